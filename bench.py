@@ -1,8 +1,16 @@
 """DS-GAN G+D train-step throughput on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N --steps K --warmup W]            # N=1 default
+    python bench.py --steps K --warmup W --dump-outputs DIR    # + the last timed step's outputs as DIR/*.npy
+    python bench.py --full [--steps K --warmup W]              # + roofline, train.py iteration, quality, cpu_baseline
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline figure needs: it builds the model, warms up, times K steps
+(no kernel timer: the captured graphs hold the step's own launches only), writes the outputs when
+--dump-outputs is given and prints the result line (metric, value, unit, ms_per_step, ...).  Every
+other leg below runs under --full only; there the per-launch HIP events of the roofline leg are
+recorded inside the timed steps, as they always were, so a --full ``value`` carries their cost.
 
 A "step" is one Pix2PixModel.optimize_parameters (DSGAN/models/pix2pix_model.py:201-217):
 G forward, D update (2 D passes + backward + Adam), G update (D pass, L1, VGG16 x2, TV, SSIM,
@@ -10,7 +18,8 @@ G backward + Adam), with the RCCL gradient all-reduces when N > 1.  Workload = B
 config 2 per GPU: 256x256 pairs, batch 16 per GPU, bf16 MFMA operands (fp32 accumulate and
 fp32 master weights/activations), synthetic inputs resident in HBM, weak scaling.
 
-Printed JSON (rank 0): value = image-pairs/s over all ranks; "roofline" for the dominant kernel
+Printed JSON (rank 0): value = image-pairs/s over all ranks, ms_per_step = the wall time of one
+timed step.  With --full also: "roofline" for the dominant kernel
 family: its algorithmic FLOPs and bytes per launch (every operand read / written once, in its
 stored dtype) over the HIP-event time of its launches in the timed region, bound = the resource
 that work needs longest at peak (dense bf16 MFMA 2.5 PF/s, HBM 8 TB/s), plus the PMC traffic
@@ -22,6 +31,7 @@ same 10-step run) at N=1 only.
 import argparse
 import json
 import os
+import random
 import sys
 import time
 
@@ -236,6 +246,47 @@ def roofline_block(ig, fams, timing_steps, peak, roof_src, pmc_t=None, pmc_t_src
 
 EAGER_TIMING_STEPS = 2   # eager steps timed after the region when graph-node events are unreadable
 
+DUMP_SAMPLE = 1 << 21    # elements kept of a flat G parameter / gradient vector (22.4 M at 256^2)
+DUMP_IMAGE_MAX = 1 << 22  # fake_B is written whole up to this many elements (3.1 M at 256^2, batch 16)
+DUMP_SEED = 20
+LOSS_NAMES = ("loss_G", "loss_G_GAN", "loss_G_L1", "loss_vgg", "tv_loss", "loss_ssim",
+              "loss_D", "loss_D_real", "loss_D_fake")
+
+
+def dump_outputs(model, out_dir):
+    """What one optimize_parameters leaves with its caller, as float32 ``out_dir/<name>.npy``:
+    fake_B, the step's losses (``losses.npy``, in LOSS_NAMES order), and the gradients and post-step
+    parameters of D (whole) and G (a fixed seeded sample of DUMP_SAMPLE elements, indices sorted),
+    each flattened in ``module.parameters()`` order.  About 35 MB at the bench shape; at most
+    4 * (DUMP_IMAGE_MAX + 4 * DUMP_SAMPLE) bytes = 50 MB at any shape (a larger fake_B is sampled the
+    same way, as ``fake_B_sample``)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    if model.fake_B.is_cuda:
+        torch.cuda.synchronize()
+
+    def scalar(v):   # (a disabled loss term is a python 0)
+        return v.detach().item() if torch.is_tensor(v) else float(v)
+
+    def sample_index(n, limit, device):   # None: keep all n elements
+        if n <= limit:
+            return None
+        g = torch.Generator().manual_seed(DUMP_SEED)
+        return torch.randint(0, n, (limit,), generator=g).sort().values.to(device)
+    fb = model.fake_B.detach()
+    idx = sample_index(fb.numel(), DUMP_IMAGE_MAX, fb.device)
+    out = {"fake_B" if idx is None else "fake_B_sample": (fb if idx is None else fb.reshape(-1)[idx]).float().cpu(),
+           "losses": torch.tensor([scalar(getattr(model, k, 0)) for k in LOSS_NAMES], dtype=torch.float32)}
+    for tag, net in (("G", model.netG), ("D", model.netD)):
+        ps = list(net.parameters())
+        flat = {"params": torch.cat([p.detach().reshape(-1) for p in ps]),
+                "grads": torch.cat([p.grad.detach().reshape(-1) for p in ps])}
+        idx = sample_index(flat["params"].numel(), DUMP_SAMPLE, flat["params"].device)
+        for k, v in flat.items():
+            out["%s_%s%s" % (k, tag, "" if idx is None else "_sample")] = (v if idx is None else v[idx]).float().cpu()
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v.numpy())
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -246,6 +297,11 @@ def main():
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp16", "fp32"],
                     help="MFMA operand type (fp32 accumulation); configs[4] names fp16")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: roofline (kernel timer), train.py-"
+                         "equivalent iteration, quality and cpu_baseline; the options below select among them")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-quality", action="store_true", help="skip the MS-SSIM delta leg")
     ap.add_argument("--cpu-threads", type=int, default=None,
@@ -254,6 +310,8 @@ def main():
     ap.add_argument("--no-train-equiv", action="store_true",
                     help="skip the train.py-equivalent iteration leg (profiling runs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -270,6 +328,7 @@ def main():
 
     dsgan_hip.require_gpu()
     torch.manual_seed(20)
+    random.seed(20)   # one process: the ImagePool draws from the global python `random`
     opt = default_train_opt(gpu_ids=[local], precision=args.precision, batchSize=args.batch)
     model = create_model(opt)
     A, B = synth_pair(args.batch, args.size, seed=rank)
@@ -279,7 +338,7 @@ def main():
     graphed = bool(getattr(model, "cuda_graph", False))
     nwarm = max(args.warmup, 2) if graphed else args.warmup   # eager step + capture, both untimed
     for w in range(nwarm):
-        if graphed and w == 1:
+        if args.full and graphed and w == 1:
             # the per-launch HIP events of the roofline leg are recorded INSIDE the captured graphs
             # (the capture happens in this call): every replay re-records them, and the leg reads the
             # last timed replay's
@@ -288,9 +347,10 @@ def main():
         model.optimize_parameters()
     torch.cuda.synchronize()
 
-    if not graphed:
-        HF.IGEMM_TIMER.reset()
-    HF.IGEMM_TIMER.on = True
+    if args.full:
+        if not graphed:
+            HF.IGEMM_TIMER.reset()
+        HF.IGEMM_TIMER.on = True
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -301,18 +361,23 @@ def main():
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
-    HF.IGEMM_TIMER.on = False
+    if args.full:
+        HF.IGEMM_TIMER.on = False
     if world > 1:
         t = torch.tensor([dt], device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
+    if args.dump_outputs and rank == 0:   # before any leg below steps the model again
+        dump_outputs(model, args.dump_outputs)
     roof_src = "HIP events inside the captured graphs, last timed replay" if graphed else "HIP events, timed steps"
     # the graph's event nodes are re-recorded by every replay, so a readable record covers ONE step
     timing_steps = 1 if graphed else args.steps
+    ig = None
     try:
-        ig = HF.IGEMM_TIMER.summary()
-        if ig["launches"] == 0:
-            raise RuntimeError("no timer records")
+        if args.full:
+            ig = HF.IGEMM_TIMER.summary()
+            if ig["launches"] == 0:
+                raise RuntimeError("no timer records")
     except Exception:   # noqa: BLE001 -- events recorded by graph nodes unreadable: time eager steps
         torch.cuda.synchronize()
         HF.IGEMM_TIMER.reset()
@@ -331,7 +396,7 @@ def main():
     # get_img_tir / get_img_gen forward / get_img_label and the per-iteration SSIM + PSNR of image 0
     # (device-side, util/metrics.py) -- timed separately, never part of `value`
     n_tp, dt_tp = 0, None
-    if not args.no_train_equiv:
+    if args.full and not args.no_train_equiv:
         from util.metrics import TrainMetrics
         metrics = TrainMetrics(model.device)
         n_tp = max(1, args.steps)
@@ -354,14 +419,12 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt_tp = t.item()
 
-    fams = HF.IGEMM_TIMER.families()
-    pw_ms = HF.IGEMM_TIMER.pw_kernel_ms()   # the pointwise GEMM kernels alone (no split-K finishing pass)
+    if args.full:
+        fams = HF.IGEMM_TIMER.families()
+        pw_ms = HF.IGEMM_TIMER.pw_kernel_ms()   # the pointwise GEMM kernels alone (no split-K finishing pass)
     if rank == 0:
         imgs = args.batch * args.steps * world
         peak = PEAK_F32_TFLOPS if args.precision == "fp32" else PEAK_BF16_TFLOPS   # dense fp16 = bf16 rate
-        pmc_t, pmc_t_src = _profile_json("pmc_traffic.json")
-        pmc_m, pmc_m_src = _profile_json("mfma_pmc.json")
-        roof = roofline_block(ig, fams, timing_steps, peak, roof_src, pmc_t, pmc_t_src, pmc_m, pmc_m_src, pw_ms=pw_ms)
         out = {
             "metric": METRIC,
             "value": round(imgs / dt, 3),
@@ -392,23 +455,30 @@ def main():
                                             "--precision fp16)" % args.precision)
                                            if (args.size, args.batch) == (512, 8) else
                                            "off-baseline shape %dx%d, batch %d" % (args.size, args.size, args.batch))},
-            "roofline": roof,
+        }
+        if args.dump_outputs:
+            out["dumped_outputs"] = args.dump_outputs
+        if args.full:
+            pmc_t, pmc_t_src = _profile_json("pmc_traffic.json")
+            pmc_m, pmc_m_src = _profile_json("mfma_pmc.json")
+            out["roofline"] = roofline_block(ig, fams, timing_steps, peak, roof_src, pmc_t, pmc_t_src, pmc_m, pmc_m_src,
+                                             pw_ms=pw_ms)
             # the whole step against the dense MFMA peak: SURVEY.md section 8(d)'s algorithmic work per
             # image pair (367.02 GFLOP at 256^2: G fwd+bwd 244.5, D 13.0, VGG16 2 fwd + 1 data-grad 109.5)
-            "step_roofline": {"gflop_per_img": STEP_GFLOP_PER_IMG if args.size == 256 else None,
-                              "achieved_tflops": round(STEP_GFLOP_PER_IMG * imgs / dt / 1e3, 1) if args.size == 256 else None,
-                              "peak_tflops": peak,
-                              "frac": round(STEP_GFLOP_PER_IMG * imgs / dt / 1e3 / peak, 4) if args.size == 256 else None,
-                              "counted_conv_gflop_per_img": round(ig["flops"] / timing_steps / 1e9 / args.batch, 2),
-                              "source": "SURVEY.md 8(d); counted = the conv launches IGEMM_TIMER saw"},
-        }
+            out["step_roofline"] = {
+                "gflop_per_img": STEP_GFLOP_PER_IMG if args.size == 256 else None,
+                "achieved_tflops": round(STEP_GFLOP_PER_IMG * imgs / dt / 1e3, 1) if args.size == 256 else None,
+                "peak_tflops": peak,
+                "frac": round(STEP_GFLOP_PER_IMG * imgs / dt / 1e3 / peak, 4) if args.size == 256 else None,
+                "counted_conv_gflop_per_img": round(ig["flops"] / timing_steps / 1e9 / args.batch, 2),
+                "source": "SURVEY.md 8(d); counted = the conv launches IGEMM_TIMER saw"}
         if dt_tp:
             out["train_py_equiv"] = {
                 "iters_per_s": round(n_tp / dt_tp, 3), "img_per_s": round(args.batch * world * n_tp / dt_tp, 3),
                 "ms_per_iter": round(dt_tp / n_tp * 1e3, 3), "iters": n_tp,
                 "what": "DSGAN/train.py:106-124 iteration: set_input + optimize_parameters + get_img_tir + "
                         "get_img_gen (forward) + get_img_label + per-iteration SSIM/PSNR of image 0"}
-        if world == 1 and not (args.no_cpu_baseline and args.no_quality):
+        if args.full and world == 1 and not (args.no_cpu_baseline and args.no_quality):
             try:
                 q, cpu = reference_legs(steps=args.quality_steps, batch=args.batch, size=args.size,
                                         threads=args.cpu_threads)

@@ -1,5 +1,6 @@
 """bench.py's roofline arithmetic with a fake kernel timer (no GPU): every per-step figure
-divides by the steps the timer actually recorded, not by --steps."""
+divides by the steps the timer actually recorded, not by --steps; and the
+--dump-outputs writer and the --full switch on stand-in objects."""
 import os
 import sys
 
@@ -90,6 +91,72 @@ def test_rocprof_family_average(tmp_path):
                  '"dsg::split_canon_kernel(dsg::RSegs)",5,50000,10000.0,1.0,1,1\n')
     avg, calls = bench.rocprof_family_avg_us(str(p), "pwgemm_kernel")
     assert calls == 40 and abs(avg - 59.5) < 1e-6
+
+
+def test_dump_outputs_writes_float32_arrays_with_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: fake_B, the losses in LOSS_NAMES order, and per network the gradients and
+    parameters in module.parameters() order -- whole up to DUMP_SAMPLE elements, above it the same
+    seeded, sorted sample of both vectors on every call."""
+    import numpy as np
+    import torch
+
+    class Model:
+        pass
+
+    torch.manual_seed(0)
+    m = Model()
+    m.netG, m.netD = torch.nn.Linear(40, 30), torch.nn.Linear(5, 3)     # 1230 and 18 elements
+    for net in (m.netG, m.netD):
+        for p in net.parameters():
+            p.grad = torch.randn_like(p)
+    m.fake_B = torch.randn(2, 3, 4, 4, dtype=torch.float64)
+    for i, k in enumerate(bench.LOSS_NAMES):
+        setattr(m, k, torch.tensor(float(i + 1), requires_grad=True) if i % 2 else float(i + 1))
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 100)
+    for d in ("a", "b"):
+        bench.dump_outputs(m, str(tmp_path / d))
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(got) == ["fake_B", "grads_D", "grads_G_sample", "losses", "params_D", "params_G_sample"]
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert np.array_equal(got["fake_B"], m.fake_B.float().numpy())
+    assert got["losses"].tolist() == [float(i + 1) for i in range(len(bench.LOSS_NAMES))]
+    flat = lambda net, grad: torch.cat([(p.grad if grad else p.detach()).reshape(-1) for p in net.parameters()]).numpy()
+    assert np.array_equal(got["params_D"], flat(m.netD, False)) and np.array_equal(got["grads_D"], flat(m.netD, True))
+    pg, gg = flat(m.netG, False), flat(m.netG, True)
+    assert got["params_G_sample"].shape == got["grads_G_sample"].shape == (100,)
+    # one index set for both vectors, in increasing order: find it from the parameters
+    pos = {v: i for i, v in enumerate(pg.tolist())}
+    idx = [pos[v] for v in got["params_G_sample"].tolist()]
+    assert idx == sorted(idx) and np.array_equal(got["grads_G_sample"], gg[idx])
+    for f in os.listdir(tmp_path / "a"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+    # an image batch above DUMP_IMAGE_MAX is sampled the same way, under another name
+    monkeypatch.setattr(bench, "DUMP_IMAGE_MAX", 50)
+    bench.dump_outputs(m, str(tmp_path / "c"))
+    assert not os.path.exists(tmp_path / "c" / "fake_B.npy")
+    fs = np.load(tmp_path / "c" / "fake_B_sample.npy")
+    assert fs.shape == (50,) and fs.dtype == np.float32 and np.isin(fs, got["fake_B"]).all()
+
+
+def test_plain_run_keeps_the_other_legs_behind_full(monkeypatch):
+    """--full is off by default, on when given; --dump-outputs takes a directory."""
+    import argparse
+    seen = {}
+    real = argparse.ArgumentParser.parse_args
+
+    def parse(self, *a, **k):
+        seen["args"] = real(self, *a, **k)
+        raise SystemExit(0)   # stop main() before it touches the GPU
+    monkeypatch.setattr(argparse.ArgumentParser, "parse_args", parse)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", "d"])
+    with pytest.raises(SystemExit):
+        bench.main()
+    a = seen["args"]
+    assert (a.full, a.steps, a.warmup, a.dump_outputs) == (False, 7, 2, "d")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    with pytest.raises(SystemExit):
+        bench.main()
+    assert seen["args"].full is True and seen["args"].dump_outputs is None
 
 
 @pytest.mark.parametrize("tag", ["a", "final"])

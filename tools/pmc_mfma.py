@@ -71,7 +71,7 @@ def main():
         if r.get("SQ_LDS_IDX_ACTIVE"):
             r["lds_conflict_frac"] = r.get("SQ_LDS_BANK_CONFLICT", 0.0) / r["SQ_LDS_IDX_ACTIVE"]
         res[f] = {k: (round(v, 4) if isinstance(v, float) else v) for k, v in sorted(r.items())}
-    json.dump({"source": "rocprofv3 --pmc passes over `bench.py --steps 3 --warmup 1` (tools/gpu_mfma_pmc.sh)",
+    json.dump({"source": "rocprofv3 --pmc passes over `bench.py --full --steps 3 --warmup 1` (tools/gpu_mfma_pmc.sh)",
                "families": res}, open(out_path, "w"), indent=1)
     order = sorted(res, key=lambda f: -res[f]["dur_us"] * res[f]["launches"])
     for f in order[:20]:

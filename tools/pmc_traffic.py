@@ -36,7 +36,7 @@ for f in sorted(set(fe) & set(wr)):
     write = kb_w * 1024 / n2
     out[f] = {"launches": n, "fetch_bytes_per_launch": round(fetch), "write_bytes_per_launch": round(write),
               "traffic_bytes_per_launch": round(fetch + write), "avg_profiled_us": round(d / n / 1e3, 1)}
-json.dump({"source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE over `bench.py --steps 3 --warmup 1` "
+json.dump({"source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE over `bench.py --full --steps 3 --warmup 1` "
                      "(FETCH_SIZE x2, gfx950 correction)", "families": out}, open(sys.argv[3], "w"), indent=1)
 for f, v in sorted(out.items(), key=lambda kv: -kv[1]["traffic_bytes_per_launch"] * kv[1]["launches"])[:15]:
     print("%-28s %5d launches  %8.1f MB/launch  (%.1f us)" % (f, v["launches"], v["traffic_bytes_per_launch"] / 1e6,
