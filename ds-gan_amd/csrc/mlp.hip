@@ -82,6 +82,8 @@ struct MlpArgs {
   int h_bf16;
   float* ws;                        // (weight-grad kernel) per-split partials, see mlp_wgrad_kernel
   int splits;
+  const float* x; long x_bs;        // (forward with the block's 1x1 shortcut, SC) block input [nb][C][HW]
+  const void* wsc;                  // (SC) shortcut weight [P][C], 16-bit
 };
 
 __device__ __forceinline__ int xcd_tile(int id, int nwg) {
@@ -304,7 +306,15 @@ __device__ __forceinline__ void glds_chunk(void* W1d, void* W2d, const void* w1v
 // gelu(z) (see qswap).  The two hidden halves' partial outputs meet once, through LDS, in a fixed
 // order (acc[wm 0] + acc[wm 1]: deterministic).  Weight chunks are double-buffered and filled by
 // LDS-DMA one chunk ahead: one barrier per chunk.
-template <typename T16, int C, int P, int MINB>
+// SC: the block's 1x1 shortcut S = Ws x is part of the tile, formed in the epilogue: once the chunk
+// loop is over (the h fragments and the weight buffers are dead), the x tile [C x BN] (fp32, rounded
+// to the 16-bit type like a GEMM operand load) is staged where h was, and the wave that finishes
+// output tile pt (pt % 2 == wm) forms S for it in one fp32 accumulator from zero, channel steps
+// ascending -- the sum the pointwise GEMM forms -- and writes (out +) S + (acc[wm 0] + acc[wm 1]):
+// the bits of the shortcut GEMM followed by this kernel accumulating on its output.  (Held across
+// the chunk loop, S would not fit the 128 / 256 registers of these kernels.)  Ws fragments come
+// straight from global memory: [P][C] 16-bit is at most 64 KB and stays in L2.
+template <typename T16, int C, int P, int MINB, bool SC = false>
 __global__ __launch_bounds__(512, MINB) void mlp_fwd_kernel(MlpArgs g) {
   typedef hx8<T16> mbf16x8;
   typedef hx4<T16> mbf16x4;
@@ -401,23 +411,63 @@ __global__ __launch_bounds__(512, MINB) void mlp_fwd_kernel(MlpArgs g) {
       for (int r = 0; r < 16; ++r) red[((wn * PT + pt) * 16 + r) * 64 + lane] = oacc[pt][r];
   __syncthreads();
   float* ob = g.out + (long)img * g.out_bs + p0 + wn * 32 + lr;
+  if constexpr (SC) {
 #pragma unroll
-  for (int pt = 0; pt < PT; ++pt)
-    if ((pt & 1) == wm)
+    for (int pt = 0; pt < PT; ++pt)
+      if ((pt & 1) == wm)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float o = red[((wn * PT + pt) * 16 + r) * 64 + lane];
-        const float v = wm == 0 ? oacc[pt][r] + o : o + oacc[pt][r];   // acc[wm 0] + acc[wm 1]
-        float* d = ob + (long)(pt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * g.HW;
-        *d = g.accumulate ? *d + v : v;
+        for (int r = 0; r < 16; ++r) {
+          const float o = red[((wn * PT + pt) * 16 + r) * 64 + lane];
+          oacc[pt][r] = wm == 0 ? oacc[pt][r] + o : o + oacc[pt][r];   // acc[wm 0] + acc[wm 1]
+        }
+    __syncthreads();   // every wave has read its partner's tiles: x takes the buffer
+    // the lane index read afresh: the staging and fragment offsets below are then formed here and
+    // not carried through the chunk loop (at 128 registers they were spilled across it)
+    const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    stage_rows<C, BN, HSTR, NT>(smem, g.x + (long)img * g.x_bs + p0, g.HW, wave * 64 + ln);
+    __syncthreads();
+    mbf16x8 xb[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks)
+      xb[ks] = mtr_frag(smem + (ks * 16 + 8 * (ln >> 5) + ((ln >> 2) & 3)) * HSTR + wn * 32 + 16 * ((ln >> 4) & 1) +
+                            4 * (ln & 3), HSTR);
+    const T16* wsr = (const T16*)g.wsc + lr * C + lh * 8;
+#pragma unroll
+    for (int pt = 0; pt < PT; ++pt)
+      if ((pt & 1) == wm) {
+        mf32x16 sacc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sacc[r] = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks)
+          sacc = mfma16(*reinterpret_cast<const mbf16x8*>(wsr + pt * 32 * C + ks * 16), xb[ks], sacc);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          float* d = ob + (long)(pt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * g.HW;
+          const float s = g.accumulate ? *d + sacc[r] : sacc[r];   // the shortcut GEMM's out
+          *d = s + oacc[pt][r];
+        }
       }
+  } else {
+#pragma unroll
+    for (int pt = 0; pt < PT; ++pt)
+      if ((pt & 1) == wm)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float o = red[((wn * PT + pt) * 16 + r) * 64 + lane];
+          const float v = wm == 0 ? oacc[pt][r] + o : o + oacc[pt][r];   // acc[wm 0] + acc[wm 1]
+          float* d = ob + (long)(pt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * g.HW;
+          *d = g.accumulate ? *d + v : v;
+        }
+  }
 }
 
 // Forward for small C (C = 64: only 4 hidden chunks per tile, where the register-resident h of
 // mlp_fwd_kernel costs the second workgroup per CU): h staged once into LDS and read by every
 // chunk's GEMM1; gelu(z) goes through an LDS chunk buffer (aliasing the W1 chunk) to GEMM2; weight
-// chunks register-prefetched one chunk ahead.
-template <typename T16, int C, int P, int BN, int HC, int NW, int MINB>
+// chunks register-prefetched one chunk ahead.  SC as in mlp_fwd_kernel: after the chunk loop x takes
+// Hs, and each wave writes (out +) Ws x + its own output tiles (no cross-wave sum here).
+template <typename T16, int C, int P, int BN, int HC, int NW, int MINB, bool SC = false>
 __global__ __launch_bounds__(NW * 64, MINB) void mlp_fwd_lds_kernel(MlpArgs g) {
   typedef hx8<T16> mbf16x8;
   typedef hx4<T16> mbf16x4;
@@ -540,16 +590,36 @@ __global__ __launch_bounds__(NW * 64, MINB) void mlp_fwd_lds_kernel(MlpArgs g) {
 
   // ---- epilogue ----
   float* ob = g.out + (long)img * g.out_bs + p0;
+  if constexpr (SC) {   // (the loop's last barrier: every wave is done with Hs)
+    stage_rows<C, BN, HSTR, NT>(Hs, g.x + (long)img * g.x_bs + p0, g.HW, tid);
+    __syncthreads();
+  }
 #pragma unroll
   for (int i = 0; i < OG::TM; ++i)
 #pragma unroll
     for (int t = 0; t < OG::TN; ++t) {
       const int n = wn * (BN / OG::WN) + t * 32 + lr;
+      mf32x16 sacc;
+      if constexpr (SC) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sacc[r] = 0.f;
+        const T16* wsr = (const T16*)g.wsc + (wm * (P / 2) + i * 32 + lr) * C + lh * 8;
+#pragma unroll
+        for (int ks = 0; ks < C / 16; ++ks)
+          sacc = mfma16(*reinterpret_cast<const mbf16x8*>(wsr + ks * 16),
+                        mtr_frag(Hs + (ks * 16 + 8 * lh + tq) * HSTR + wn * (BN / OG::WN) + t * 32 + 16 * tG + 4 * tp, HSTR),
+                        sacc);
+      }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int m = wm * (P / 2) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
         float* o = ob + (long)m * g.HW + n;
-        *o = g.accumulate ? *o + oacc[i][t][r] : oacc[i][t][r];
+        if constexpr (SC) {
+          const float sv = g.accumulate ? *o + sacc[r] : sacc[r];   // the shortcut GEMM's out
+          *o = sv + oacc[i][t][r];
+        } else {
+          *o = g.accumulate ? *o + oacc[i][t][r] : oacc[i][t][r];
+        }
       }
     }
 }
@@ -1061,7 +1131,9 @@ __global__ __launch_bounds__(256, 1) void mlp_bwd_dma_kernel(MlpArgs g) {
 
   auto chunk = [&](int j, const T16* W1s, T16* Wnext) __attribute__((always_inline)) {
     // chunk j landed (this wave's pieces: the only LDS-DMA in flight) and every wave is done with
-    // chunk j-1 (its ring slot, Zn / Gn; at j = 0 the h / dy staging area = slot 1)
+    // chunk j-1 (its ring slot, Zn / Gn; at j = 0 the h / dy staging area = slot 1).  (A counted
+    // wait here, vmcnt(4), which leaves chunk j-1's copy-out stores in flight, gives the same bits
+    // and the same time: the stores are not what this wait waits for.  DESIGN.md section 6.)
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     raw_barrier();
     if (j + 1 < NCH) chunk_dma(j + 1, Wnext);
@@ -1479,12 +1551,17 @@ constexpr int MLP_NW = 8;
 template <typename T16, int C, int P, int BN, int MINB>
 static void fwd_lds_launch(const MlpArgs& g, hipStream_t st) {
   const unsigned tiles = (unsigned)((long)g.nb * (g.HW / BN));
-  hipLaunchKernelGGL((mlp_fwd_lds_kernel<T16, C, P, BN, 64, MLP_NW, MINB>), dim3(tiles), dim3(MLP_NW * 64), 0, st, g);
+  if (g.x)
+    hipLaunchKernelGGL((mlp_fwd_lds_kernel<T16, C, P, BN, 64, MLP_NW, MINB, true>), dim3(tiles), dim3(MLP_NW * 64), 0, st,
+                       g);
+  else
+    hipLaunchKernelGGL((mlp_fwd_lds_kernel<T16, C, P, BN, 64, MLP_NW, MINB>), dim3(tiles), dim3(MLP_NW * 64), 0, st, g);
 }
 template <typename T16, int C, int P, int MINB>
 static void fwd_launch(const MlpArgs& g, hipStream_t st) {
   const unsigned tiles = (unsigned)((long)g.nb * (g.HW / 128));
-  hipLaunchKernelGGL((mlp_fwd_kernel<T16, C, P, MINB>), dim3(tiles), dim3(512), 0, st, g);
+  if (g.x) hipLaunchKernelGGL((mlp_fwd_kernel<T16, C, P, MINB, true>), dim3(tiles), dim3(512), 0, st, g);
+  else hipLaunchKernelGGL((mlp_fwd_kernel<T16, C, P, MINB>), dim3(tiles), dim3(512), 0, st, g);
 }
 // backward: 8 waves x 128 pixels where the LDS tiles fit, else 4 waves x 64 pixels (same bsum
 // granularity: one partial row per 32 pixels)
@@ -1492,7 +1569,9 @@ static void fwd_launch(const MlpArgs& g, hipStream_t st) {
 // weight ring (0.831 -> 0.717 ms at uc3, B = 16, same bits; profiles/r04/mlp_micro.txt), 1 the
 // register-staged weights, 2 the DMA ring with precomputed LDS / DMA addresses (mlp_bwd_dma_kernel,
 // default: 0.733 -> 0.704 ms, same bits; profiles/r04/mlp_micro_b.txt).  (An 8-wave form -- two waves per SIMD, 128-row hidden chunks -- measured
-// 0.977 ms: at 256 registers it spills, and it issues more VALU per MFMA.)
+// 0.977 ms: at 256 registers it spills, and it issues more VALU per MFMA.  Form 2 with a counted wait
+// that keeps the copy-out stores in flight across chunks: 0.693-0.697 ms either way, same bits;
+// profiles/r07/mlp_micro_ab_form3.txt -- not kept.)
 static int g_mlp_tune[4] = {2, 0, 0, 0};
 
 template <typename T16, int C, int P, int BN, int NW, bool GD = true, int MINB = 1, bool DMA = false>
@@ -1536,16 +1615,20 @@ int dsgan_mlp_supported(int C, int P, int HW) {
   return 32;
 }
 
-int dsgan_mlp_fwd(const void* h, long h_bs, int h_bf16, const void* w1, const float* b1, const void* w2,
-                  const float* b2, float* out, long out_bs, int nb, int C, int P, int HW,
-                  int accumulate, hipStream_t st) {
+// x != NULL: the forward with the block's 1x1 shortcut, out (+)= ws x + b2 + W2 gelu(W1 h + b1)
+static int mlp_fwd_impl(const void* h, long h_bs, int h_bf16, const void* w1, const float* b1, const void* w2,
+                        const float* b2, const float* x, long x_bs, const void* ws, float* out, long out_bs, int nb,
+                        int C, int P, int HW, int accumulate, hipStream_t st) {
   DSG_REQUIRE(h && w1 && b1 && w2 && out && nb > 0, "dsgan_mlp_fwd: bad args");
   DSG_REQUIRE(dsgan_mlp_supported(C, P, HW), "dsgan_mlp_fwd: unsupported shape C=%d P=%d HW=%d", C, P, HW);
   DSG_REQUIRE(((uintptr_t)h & 15) == 0 && (h_bs & 7) == 0 && ((uintptr_t)w1 & 15) == 0 && ((uintptr_t)w2 & 15) == 0,
               "dsgan_mlp_fwd: operands must be 16-byte aligned");
+  DSG_REQUIRE(!x || (ws && ((uintptr_t)x & 15) == 0 && (x_bs & 3) == 0 && ((uintptr_t)ws & 15) == 0),
+              "dsgan_mlp_fwd_sc: x and ws must be 16-byte aligned, the x batch stride a multiple of 4");
   MlpArgs g{};
   g.h = h; g.h_bs = h_bs; g.w1 = w1; g.b1 = b1; g.w2 = w2; g.b2 = b2;
   g.out = out; g.out_bs = out_bs; g.HW = HW; g.nb = nb; g.accumulate = accumulate; g.h_bf16 = h_bf16;
+  g.x = x; g.x_bs = x_bs; g.wsc = ws;
   // MINB = waves per SIMD: 4 (two workgroups per CU) where 128 registers hold
   with_half([&](auto* t) {
     using T16 = std::remove_pointer_t<decltype(t)>;
@@ -1556,6 +1639,22 @@ int dsgan_mlp_fwd(const void* h, long h_bs, int h_bf16, const void* w1, const fl
   });
   DSG_CHECK_LAUNCH();
   return 0;
+}
+
+int dsgan_mlp_fwd(const void* h, long h_bs, int h_bf16, const void* w1, const float* b1, const void* w2,
+                  const float* b2, float* out, long out_bs, int nb, int C, int P, int HW,
+                  int accumulate, hipStream_t st) {
+  return mlp_fwd_impl(h, h_bs, h_bf16, w1, b1, w2, b2, nullptr, 0, nullptr, out, out_bs, nb, C, P, HW, accumulate, st);
+}
+
+// The block tail in one launch: out (+)= ws x + b2 + W2 gelu(W1 h + b1).  x [nb][C][HW] fp32 (batch
+// stride x_bs) is the block's input, ws [P][C] the 16-bit copy of the 1x1 shortcut weight;
+// `accumulate` adds the caller's out, as in dsgan_mlp_fwd.
+int dsgan_mlp_fwd_sc(const void* h, long h_bs, int h_bf16, const void* w1, const float* b1, const void* w2,
+                     const float* b2, const float* x, long x_bs, const void* ws, float* out, long out_bs, int nb,
+                     int C, int P, int HW, int accumulate, hipStream_t st) {
+  DSG_REQUIRE(x && ws, "dsgan_mlp_fwd_sc: bad args");
+  return mlp_fwd_impl(h, h_bs, h_bf16, w1, b1, w2, b2, x, x_bs, ws, out, out_bs, nb, C, P, HW, accumulate, st);
 }
 
 int dsgan_mlp_bwd(const void* h, long h_bs, int h_bf16, const float* dy, long dy_bs, const void* w1, const float* b1,

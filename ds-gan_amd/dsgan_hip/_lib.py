@@ -57,6 +57,7 @@ SIGNATURES = {
     # mlp.hip
     "dsgan_mlp_supported": [I, I, I],
     "dsgan_mlp_fwd": [P, L, I, P, P, P, P, P, L, I, I, I, I, I, S],
+    "dsgan_mlp_fwd_sc": [P, L, I, P, P, P, P, P, L, P, P, L, I, I, I, I, I, S],
     "dsgan_mlp_bwd": [P, L, I, P, L, P, P, P, P, L, P, P, P, I, I, I, I, S],
     "dsgan_mlp_wgrad_workspace": [I, I, I, I],
     "dsgan_mlp_wgrad": [P, L, I, P, L, P, P, P, P, P, P, P, L, I, I, I, I, S],

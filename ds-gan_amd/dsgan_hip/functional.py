@@ -1095,6 +1095,12 @@ def _mlp_tile(C, P, HW, x):
     return int(_lib.load().dsgan_mlp_supported(C, P, HW))
 
 
+# The fused block tail takes the block's 1x1 shortcut into its forward kernel (dsgan_mlp_fwd_sc): one
+# launch, and out is written once instead of written, re-read and re-written.  (=0: shortcut GEMM,
+# then dsgan_mlp_fwd accumulating on it, for A/B runs)
+MLP_FOLD_SC = [os.environ.get("DSGAN_MLP_FOLD_SC", "1") != "0"]
+
+
 def _mlp_flops(N, C, P, HW):
     # algorithmic MACs of the two Linear layers (fwd; each of dgrad/wgrad is the same count)
     return 2.0 * N * HW * (4 * C * C + 4 * C * P)
@@ -1106,9 +1112,10 @@ class PwMlpFn(torch.autograd.Function):
 
     In bf16 mode h is stored bf16 (dsgan_instnorm_fwd_bf16): its only readers are bf16-operand
     MFMA GEMMs that round it to bf16 on load anyway, so this halves its bytes and changes no bit.
-      * fused shapes (mlp.hip): forward out = Ws x (pwgemm), then out += W2 gelu(W1 h + b1) + b2 in
-        one kernel -- z is never stored; backward recomputes z and writes only bf16 gelu(z) and dz
-        for the two weight-grads.
+      * fused shapes (mlp.hip): forward out = Ws x + W2 gelu(W1 h + b1) + b2 in one kernel
+        (dsgan_mlp_fwd_sc; MLP_FOLD_SC off or a misaligned x: out = Ws x by pwgemm, then
+        dsgan_mlp_fwd accumulating on it) -- z is never stored; backward recomputes z and writes
+        only bf16 gelu(z) and dz for the two weight-grads.
       * other bf16 shapes with HW % 128 == 0: pwconv1 evaluates GELU once and writes g = gelu(z) and
         gp = gelu'(z), both bf16; backward writes dz = (W2^T dy) * gp in bf16 (again exactly what
         its two GEMM readers would round to) with the b1 grad summed from the fp32 values in the
@@ -1161,6 +1168,17 @@ class PwMlpFn(torch.autograd.Function):
         hb = int(h.dtype != torch.float32)
         ctx.hb = hb
         ctx.tile = tile
+        if tile and MLP_FOLD_SC[0]:
+            x4, xbs = nchw(x)
+            if x4.data_ptr() % 16 == 0 and xbs % 4 == 0 and ws.is_contiguous():
+                out = out0 if out0 is not None else _empty(N, P, H, W, h)
+                e0 = IGEMM_TIMER.begin()
+                call("dsgan_mlp_fwd_sc", ptr(h), hbs, hb, ptr(bf16_weight(w1)), ptr(b1), ptr(bf16_weight(w2)), ptr(b2),
+                     ptr(x4), xbs, ptr(bf16_weight(ws)), ptr(out), obs, N, C, P, HW, int(acc1), stream())
+                IGEMM_TIMER.end(e0, _mlp_flops(N, C, P, HW) + 2.0 * N * HW * C * P, ("mlp_fwd", N, C, H, W, P, 1, 1),
+                                "mlp_fwd_kernel", _nb(h, w1, b1, w2, b2, x4, ws) + (2 if acc1 else 1) * _nb(out))
+                ctx.save_for_backward(h, x, ws)
+                return acc if acc1 else out
         if tile:
             out = conv_fwd_raw(x, ws, None, 1, 0, out=out0, accumulate=acc1)
             e0 = IGEMM_TIMER.begin()
@@ -1370,8 +1388,8 @@ def pw_mlp(h, x, w1, b1, w2, b2, ws, norm=False, slot=None, acc=None):
     """ConvNeXt block tail; with norm=True the first argument is the depthwise-conv output d and
     the block's InstanceNorm h = IN(d) is applied inside (MixConvNeXtML.py:219-224).  ``slot``
     (CatSlot): the output is written into the slot's tail and returned as that alias.  ``acc``: the
-    output is summed into acc in place (acc + block, the shortcut GEMM's epilogue adds acc) and acc
-    is returned."""
+    output is summed into acc in place (acc + block: the epilogue of the block's first kernel adds
+    acc) and acc is returned."""
     return PwMlpFn.apply(h, x, w1, b1, w2, b2, ws, norm, slot, acc)
 
 

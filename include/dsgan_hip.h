@@ -170,6 +170,12 @@ int dsgan_mlp_supported(int C, int P, int HW);
 int dsgan_mlp_fwd(const void* h, long h_bs, int h_bf16, const void* w1, const float* b1, const void* w2,
                   const float* b2, float* out, long out_bs, int nb, int C, int P, int HW,
                   int accumulate, hipStream_t stream);
+/* dsgan_mlp_fwd with the block's 1x1 shortcut in the same launch: out (+)= ws x + (dsgan_mlp_fwd's
+ * sum).  x [nb][C][HW] fp32 (batch stride x_bs, a multiple of 4; 16-byte aligned) is the block's
+ * input, ws [P][C] the 16-bit copy of the shortcut weight; accumulate adds the caller's out. */
+int dsgan_mlp_fwd_sc(const void* h, long h_bs, int h_bf16, const void* w1, const float* b1, const void* w2,
+                     const float* b2, const float* x, long x_bs, const void* ws, float* out, long out_bs, int nb,
+                     int C, int P, int HW, int accumulate, hipStream_t stream);
 int dsgan_mlp_bwd(const void* h, long h_bs, int h_bf16, const float* dy, long dy_bs, const void* w1,
                   const float* b1, const void* w2, float* dh, long dh_bs, void* g_out, void* dz_out,
                   float* bsum, int nb, int C, int P, int HW, hipStream_t stream);

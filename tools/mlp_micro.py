@@ -1,6 +1,7 @@
 """Time the fused MLP kernels (mlp.hip) at the DS-GAN block shapes, as the training step calls them
 (bf16 h from the block's InstanceNorm): forward, backward dh-only + weight-grad kernel, and the
-backward with bf16 g / dz written for the pwgemm weight-grads.
+backward with bf16 g / dz written for the pwgemm weight-grads; and the block tail's forward as two
+launches (shortcut GEMM + dsgan_mlp_fwd) against the one launch with the shortcut inside.
 
     python tools/mlp_micro.py            # DSGAN_HIP_LIB=<other .so> to time another build
     python tools/mlp_micro.py --libs a.so,b.so,a.so   # builds interleaved, one process each
@@ -67,6 +68,29 @@ for name, C, P, H in SHAPES:
     f(); bd(); wg(); torch.cuda.synchronize()
     cs = (out.double().sum().item(), dh.double().sum().item(), gw1.double().abs().sum().item(),
           gw2.double().abs().sum().item(), gb1.double().abs().sum().item())
+    # block tail forward: the 1x1 shortcut GEMM + dsgan_mlp_fwd accumulating on it, against the one
+    # launch with the shortcut inside (dsgan_mlp_fwd_sc, where the build has it)
+    from dsgan_hip import functional as HF
+    HF.set_precision("bf16")
+    x = torch.randn(N, C, H, H, device="cuda")
+    wsf = torch.randn(P, C, 1, 1, device="cuda") / C ** 0.5
+    wsb = wsf.bfloat16()
+
+    def two():
+        HF.conv_fwd_raw(x, wsf, None, 1, 0, out=out)
+        f()
+    sc = lambda: call("dsgan_mlp_fwd_sc", ptr(h), C * HW, 1, ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(x), C * HW, ptr(wsb),
+                      ptr(out), P * HW, N, C, P, HW, 0, stream())
+    tail = " | tail fwd shortcut+mlp %.3f" % timeit(two)
+    two(); torch.cuda.synchronize()
+    o2 = out.clone()
+    try:
+        tail += " folded %.3f ms" % timeit(sc)
+        sc(); torch.cuda.synchronize()
+        tail += " (rel diff %.2e, bitwise %s)" % (((out - o2).norm() / o2.norm()).item(), torch.equal(out, o2))
+    except (RuntimeError, AttributeError):   # an older build
+        tail += " folded n/a"
+    del x, o2
     # knob A/B of the backward with g / dz out (dsgan_mlp_tune key 0: 0 LDS-DMA ring, 1 register-staged,
     # 2 the ring with precomputed addresses)
     ab = ""
@@ -84,5 +108,5 @@ for name, C, P, H in SHAPES:
             res[1][0], res[0][0], same[0], res[2][0], same[1])
     fl = 2.0 * N * HW * (C4 * C + C4 * P)
     print("%-4s C=%4d P=%4d HW=%6d | fwd %.3f ms (%.0f TF/s) | bwd-dh %.3f | wgrad %.3f | bwd-g/dz %.3f ms | cs %s%s"
-          % (name, C, P, HW, tf, fl / tf / 1e9, tbd, twg, tbg, " ".join("%.6e" % c for c in cs), ab), flush=True)
+          % (name, C, P, HW, tf, fl / tf / 1e9, tbd, twg, tbg, " ".join("%.6e" % c for c in cs), ab + tail), flush=True)
     del h, dy, out, g, dz, dh, wsp
