@@ -10,10 +10,9 @@ False (the frozen VGG16, or D during the G step, DSGAN/models/base_model.py:171-
 weight-grad launch at all.
 """
 import contextlib
+import ctypes
 import os
 import math
-
-import ctypes
 
 import torch
 
@@ -237,6 +236,31 @@ IGEMM_TIMER = KernelTimer(kernel_only=True)
 AUX_TIMER = KernelTimer()   # the HBM-bound depthwise / InstanceNorm launches (tools/launch_table.py)
 
 
+class _timed:
+    """``with _timed(timer, flops, tag, fam, nbytes): call(...)`` -- the one place a launch is
+    bracketed with a KernelTimer's event pair; the record is (e0, e1, flops, tag, fam, nbytes).
+    With the timer off it creates no event and records nothing."""
+    __slots__ = ("timer", "rec", "e0")
+
+    def __init__(self, timer, flops, tag=None, fam="other", nbytes=0):
+        self.timer, self.rec = timer, (flops, tag, fam, nbytes)
+
+    def __enter__(self):
+        self.e0 = self.timer.begin()
+
+    def __exit__(self, etype, exc, tb):
+        if etype is None:
+            self.timer.end(self.e0, *self.rec)
+
+
+def _ws(query, *dims, like):
+    """fp32 scratch of a launch, on ``like``'s device: as many elements as the library's ``query``
+    (a ``*_workspace`` function) returns for ``dims``, None when that is 0.  Hand it to the entry
+    point through wsa(), which also makes it that call's keep-alive candidate."""
+    n = getattr(_lib.load(), query)(*dims)
+    return torch.empty(n, device=like.device, dtype=torch.float32) if n > 0 else None
+
+
 def _nb(*ts):
     """HBM bytes of the given operands (None skipped): the algorithmic traffic of a launch."""
     return float(sum(t.numel() * t.element_size() for t in ts if t is not None))
@@ -303,27 +327,53 @@ def _pw_ok(mode, M, K, P, a_bs, b_bs, a, b):
 
 
 def _tconv(X, xbs, Wt, bias, Y, ybs, gpre, gbs, nb, K, M, Hin, Win, Hout, Wout, stride, taps,
-           Hdst, Wdst, os_, ph, pw, act, gact):
-    """Wt: fp32 tap-major weights (_wtrans) or their bf16 copy (_wtrans_bf16, mode 0)."""
-    import ctypes
+           Hdst, Wdst, os_, ph, pw, act, gact, xh=False):
+    """Wt: fp32 tap-major weights (_wtrans) or their bf16 copy (_wtrans_bf16, mode 0); xh: X holds
+    the 16-bit half type (dsgan_tconv_ws_xh, bf16 weights only)."""
     dh = (ctypes.c_int * len(taps))(*[t[0] for t in taps])
     dw = (ctypes.c_int * len(taps))(*[t[1] for t in taps])
-    nws = _lib.load().dsgan_tconv_workspace(nb, K, M, Hout, Wout, len(taps))
-    ws = torch.empty(nws, device=X.device, dtype=torch.float32) if nws > 0 else None
-    call("dsgan_tconv_ws", ptr(X), xbs, ptr(Wt), ptr(bias), ptr(Y), ybs, ptr(gpre), gbs, nb, K, M, Hin,
-         Win, Hout, Wout, stride, len(taps), ctypes.cast(dh, ctypes.c_void_p),
-         ctypes.cast(dw, ctypes.c_void_p), Hdst, Wdst, os_, ph, pw, ACT[act], ACT[gact],
-         LRELU_SLOPE, int(Wt.dtype != torch.float32), *wsa(ws), stream())
+    call("dsgan_tconv_ws_xh" if xh else "dsgan_tconv_ws", ptr(X), xbs, ptr(Wt), ptr(bias), ptr(Y), ybs, ptr(gpre),
+         gbs, nb, K, M, Hin, Win, Hout, Wout, stride, len(taps), ctypes.cast(dh, ctypes.c_void_p),
+         ctypes.cast(dw, ctypes.c_void_p), Hdst, Wdst, os_, ph, pw, ACT[act], ACT[gact], LRELU_SLOPE,
+         *(() if xh else (int(Wt.dtype != torch.float32),)),
+         *wsa(_ws("dsgan_tconv_workspace", nb, K, M, Hout, Wout, len(taps), like=X)), stream())
 
 
-# Transformed-weight cache: an entry is valid while the parameter's storage pointer and the
-# global weight generation are unchanged.  FlatAdam.step() bumps the generation (weights are
-# updated in place by the fused Adam kernel, invisible to torch's version counters).
+# Cached weight copies (tap-major transforms, 16-bit casts): an entry is valid while the
+# parameter's storage pointer and the global weight generation are unchanged.  FlatAdam.step()
+# bumps the generation (weights are updated in place by the fused Adam kernel, invisible to
+# torch's version counters).
 WEIGHT_GEN = [0]
-_WT_CACHE = {}
-
-
 _PARAM_GEN = {}
+_WT_CACHE = {}     # conv weights in a kernel's layout (_wtrans, _wtrans_bf16, _vgg_wt)
+_BF16_CACHE = {}   # plain 16-bit casts (bf16_weight)
+
+
+class _Copy:
+    """A cache entry: the copy of parameter ``w`` (at storage pointer ``ptr``), built at generation
+    ``gen`` / ``w._version``.  ``mode``: the dsgan_wtrans_multi mode that rebuilds a 16-bit copy in
+    place (0-2 tap-major, -1 plain cast), None for a copy that is rebuilt at its next use."""
+    __slots__ = ("gen", "version", "w", "ptr", "copy", "mode")
+
+
+def _wgen(w):
+    return (WEIGHT_GEN[0], _PARAM_GEN.get(id(w), 0))
+
+
+def _cached(cache, w, what, build, mode=None):
+    """The copy of ``w`` that the tuple ``what`` names in ``cache``, from ``build()`` when there is
+    none or the weight has changed since (generation, ``_version``, identity)."""
+    key = (id(w), w.data_ptr(), tuple(w.shape)) + what
+    ent = cache.get(key)
+    gen = _wgen(w)
+    if ent is not None and ent.gen == gen and ent.version == w._version and ent.w is w:
+        return ent.copy
+    ent = _Copy()
+    ent.gen, ent.version, ent.w, ent.ptr, ent.copy, ent.mode = gen, w._version, w, w.data_ptr(), build(), mode
+    if cache is _BF16_CACHE and len(cache) > 8192:
+        cache.clear()
+    cache[key] = ent
+    return ent.copy
 
 
 def bump_weight_generation(params=None):
@@ -344,50 +394,30 @@ def bump_weight_generation(params=None):
 
 def _refresh_half_copies(params):
     ids = {id(p) for p in params}
-    todo = []   # (cache, key, entry, mode)
-    for cache in (_WT_CACHE, _BF16_CACHE):
-        for key, ent in cache.items():
-            w = ent[2]
-            if id(w) not in ids or key[1] != w.data_ptr() or ent[3].dtype == torch.float32:
-                continue
-            if cache is _WT_CACHE and len(key) != 5:   # (fp32 _wtrans entries are rebuilt lazily)
-                continue
-            if ent[3].dtype != half_dtype():
-                continue
-            todo.append((cache, key, ent, key[4] if cache is _WT_CACHE else -1))
+    todo = [e for cache in (_WT_CACHE, _BF16_CACHE) for e in cache.values()
+            if id(e.w) in ids and e.mode is not None and e.ptr == e.w.data_ptr() and e.copy.dtype == half_dtype()]
     if not todo:
         return
     n = len(todo)
-    src = (ctypes.c_void_p * n)(*[e[2][2].data_ptr() for e in todo])
-    dst = (ctypes.c_void_p * n)(*[e[2][3].data_ptr() for e in todo])
+    src = (ctypes.c_void_p * n)(*[e.w.data_ptr() for e in todo])
+    dst = (ctypes.c_void_p * n)(*[e.copy.data_ptr() for e in todo])
     desc = []
-    for _, _, ent, mode in todo:
-        w = ent[2]
+    for e in todo:
+        w = e.w
         Co, Ci, KH, KW = (tuple(w.shape) + (1, 1, 1))[:4] if w.dim() < 4 else tuple(w.shape)
-        if mode < 0:   # plain cast: any shape, as a flat run of numel elements
+        if e.mode < 0:   # plain cast: any shape, as a flat run of numel elements
             Co, Ci, KH, KW = w.numel(), 1, 1, 1
-        desc += [Co, Ci, KH, KW, mode]
+        desc += [Co, Ci, KH, KW, e.mode]
     dsc = (ctypes.c_int * len(desc))(*desc)
     call("dsgan_wtrans_multi", ctypes.cast(src, ctypes.c_void_p), ctypes.cast(dst, ctypes.c_void_p),
          ctypes.cast(dsc, ctypes.c_void_p), n, stream())
-    for cache, key, ent, _ in todo:
-        w = ent[2]
-        cache[key] = (_wgen(w), w._version, w, ent[3])
-
-
-def _wgen(w):
-    return (WEIGHT_GEN[0], _PARAM_GEN.get(id(w), 0))
+    for e in todo:
+        e.gen, e.version = _wgen(e.w), e.w._version
 
 
 def _wtrans(w, mode, kh0=0, kw0=0, nth=0, ntw=0):
-    key = (id(w), w.data_ptr(), tuple(w.shape), mode, kh0, kw0, nth, ntw)
-    ent = _WT_CACHE.get(key)
-    gen = _wgen(w)
-    if ent is not None and ent[0] == gen and ent[1] == w._version and ent[2] is w:
-        return ent[3]
-    wt = _wtrans_build(w, mode, kh0, kw0, nth, ntw)
-    _WT_CACHE[key] = (gen, w._version, w, wt)
-    return wt
+    """fp32 tap-major weights for tconv.hip, cached (rebuilt at the next use after an update)."""
+    return _cached(_WT_CACHE, w, (mode, kh0, kw0, nth, ntw), lambda: _wtrans_build(w, mode, kh0, kw0, nth, ntw))
 
 
 def _wtrans_build(w, mode, kh0=0, kw0=0, nth=0, ntw=0):
@@ -401,34 +431,35 @@ def _wtrans_build(w, mode, kh0=0, kw0=0, nth=0, ntw=0):
 def _wtrans_bf16(w, mode):
     """bf16 tap-major weights for pconv.hip / pconvt.hip (mode 0 forward, 1 stride-1 data-grad,
     2 stride-2 data-grad / ConvTranspose), cached."""
-    key = (id(w), w.data_ptr(), tuple(w.shape), half_dtype(), mode)
-    ent = _WT_CACHE.get(key)
-    gen = _wgen(w)
-    if ent is not None and ent[0] == gen and ent[1] == w._version and ent[2] is w:
-        return ent[3]
-    Co, Ci, KH, KW = w.shape
-    wb = torch.empty(KH * KW * Co * Ci, device=w.device, dtype=half_dtype())
-    call("dsgan_conv_wtrans_bf16", ptr(w), ptr(wb), Co, Ci, KH, KW, mode, stream())
-    _WT_CACHE[key] = (gen, w._version, w, wb)
-    return wb
+    def build():
+        Co, Ci, KH, KW = w.shape
+        wb = torch.empty(KH * KW * Co * Ci, device=w.device, dtype=half_dtype())
+        call("dsgan_conv_wtrans_bf16", ptr(w), ptr(wb), Co, Ci, KH, KW, mode, stream())
+        return wb
+    return _cached(_WT_CACHE, w, (half_dtype(), mode), build, mode)
+
+
+def bf16_weight(w):
+    """bf16 copy of a parameter for the fused kernels, cached like _wtrans (same invalidation)."""
+    def build():
+        out = torch.empty(w.shape, device=w.device, dtype=half_dtype())
+        call("dsgan_f32_to_bf16", ptr(w), ptr(out), w.numel(), stream())
+        return out
+    return _cached(_BF16_CACHE, w, (half_dtype(),), build, -1)
 
 
 def _pw_ws(M, N, P, nb, like):
     """Split-K scratch of a pointwise weight-grad (dsgan_pw_wgrad_workspace), or None."""
-    n = _lib.load().dsgan_pw_wgrad_workspace(M, N, P, nb)
-    return torch.empty(n, device=like.device, dtype=torch.float32) if n > 0 else None
+    return _ws("dsgan_pw_wgrad_workspace", M, N, P, nb, like=like)
 
+
+# Eligibility rules of the kernel families.  They take plain numbers -- pointers as integers, of
+# which only the alignment is read -- so that the choice can be asked without a tensor.
 
 def _pw_io_ok(K, P, xbs, ybs, x, y, pre=None, pbs=0):
     """dsgan_pw_fwd_io / dgrad_io alignment rules with fp32 activations (16-bit weight rows: K % 8)."""
-    return (K % 8 == 0 and P % 128 == 0 and xbs % 8 == 0 and ybs % 8 == 0 and x.data_ptr() % 16 == 0
-            and y.data_ptr() % 16 == 0 and (pre is None or (pbs % 4 == 0 and pre.data_ptr() % 16 == 0)))
-
-
-def _pw_fd_ws(mode, M, K, P, nb, like):
-    """Split-K scratch of an under-filled pointwise FWD (0) / DGRAD (1) (dsgan_pw_fd_workspace), or None."""
-    n = _lib.load().dsgan_pw_fd_workspace(mode, M, K, P, nb)
-    return torch.empty(n, device=like.device, dtype=torch.float32) if n > 0 else None
+    return (K % 8 == 0 and P % 128 == 0 and xbs % 8 == 0 and ybs % 8 == 0 and x % 16 == 0
+            and y % 16 == 0 and (pre is None or (pbs % 4 == 0 and pre % 16 == 0)))
 
 
 def _pwf_ok(mode, M, K, P, a_bs, b_bs, a, b):
@@ -438,22 +469,22 @@ def _pwf_ok(mode, M, K, P, a_bs, b_bs, a, b):
 
 def _pws_ok(K, M, P, xbs, ybs, x, y):
     """1x1 contraction with <= 16 channels on one side for pwsmall.hip (16-byte rows)."""
-    return ((K <= 16 or M <= 16) and x.data_ptr() % 16 == 0 and y.data_ptr() % 16 == 0
+    return ((K <= 16 or M <= 16) and x % 16 == 0 and y % 16 == 0
             and bool(_lib.load().dsgan_pw_small_supported(K, M, P, xbs, ybs)))
 
 
 PGLAST = [True]   # the PatchGAN head on pglast.hip (off: the generic small-channel kernels; tests / A-B)
 
 
-def _pglast_ok(Cout, Cin, KH, KW, stride, pad, H, W, w):
+def _pglast_ok(Cout, Cin, KH, KW, stride, pad, H, W, w_dim, w_contig):
     """Conv(Cin -> 1, 4x4, stride 1, pad 1): the PatchGAN head (networks.py:567-568), pglast.hip."""
-    return (PGLAST[0] and Cout == 1 and KH == 4 and KW == 4 and stride == 1 and pad == 1 and w.dim() == 4
-            and w.is_contiguous() and bool(_lib.load().dsgan_pglast_supported(Cin, H, W)))
+    return (PGLAST[0] and Cout == 1 and KH == 4 and KW == 4 and stride == 1 and pad == 1 and w_dim == 4
+            and w_contig and bool(_lib.load().dsgan_pglast_supported(Cin, H, W)))
 
 
-def _thin3_ok(M, H, W, bs_small, bs_big, t_small, t_big):
+def _thin3_ok(M, H, W, bs_small, bs_big, p_small, p_big):
     """3x3 / s1 / p1 conv with <= 4 channels on one side at W % 256 == 0 (thin3.hip)."""
-    return (t_small.data_ptr() % 16 == 0 and t_big.data_ptr() % 16 == 0
+    return (p_small % 16 == 0 and p_big % 16 == 0
             and bool(_lib.load().dsgan_thin3_supported(M, H, W, bs_small, bs_big)))
 
 
@@ -462,10 +493,101 @@ def _pconv_ok(K, KH, KW, stride):
 
 
 def _pconv(x, xbs, wb, b, y, ybs, N, K, M, H, W, Ho, Wo, KH, KW, stride, pad, act, gpre, gbs, gact, accumulate):
-    nws = _lib.load().dsgan_pconv_workspace(N, K, M, Ho, Wo)
-    ws = torch.empty(nws, device=x.device, dtype=torch.float32) if nws > 0 else None
     call("dsgan_pconv_ws", ptr(x), xbs, ptr(wb), ptr(b), ptr(y), ybs, ptr(gpre), gbs, N, K, M, H, W, Ho, Wo, KH, KW,
-         stride, pad, ACT[act], ACT[gact], LRELU_SLOPE, int(accumulate), *wsa(ws), stream())
+         stride, pad, ACT[act], ACT[gact], LRELU_SLOPE, int(accumulate),
+         *wsa(_ws("dsgan_pconv_workspace", N, K, M, Ho, Wo, like=x)), stream())
+
+
+# Which kernel family a conv takes -- the main performance fact of a layer -- as functions of plain
+# numbers and flags: shapes, batch strides, pointer values (alignment only), the weight's dim() and
+# contiguity, the epilogue options present, and the module's state (the precision, PGLAST[0],
+# WCONV_DB_FOLD).  They touch no tensor and launch nothing, so they answer on a machine without a
+# GPU (tests/test_dispatch_cpu.py).  Each returns (family, form): the family is the name the
+# timer records, the form tells the two launch forms of pwgemm_kernel ("io_ws": the cached 16-bit
+# weight through dsgan_pw_{fwd,dgrad}_io_ws, "gemm": dsgan_pw_gemm) and of wconv_kernel ("db": with
+# the bias grad folded in, "plain") apart and is None elsewhere.  The first rule that holds wins.
+
+def conv_fwd_family(Cin, H, W, Cout, KH, KW, stride, pad, xbs, ybs, pbs, x_ptr, y_ptr, w_ptr, pre_ptr,
+                    w_dim, w_contig, act, xact, accumulate):
+    pw = KH == 1 and KW == 1 and stride == 1 and pad == 0
+    if (KH == 3 and KW == 3 and stride == 1 and pad == 1 and act is None and pre_ptr is None and xact is None
+            and w_contig and _thin3_ok(Cout, H, W, ybs, xbs, y_ptr, x_ptr)):
+        return "thin3_kernel", None      # 3x3 into <= 4 channels at full resolution (the G head)
+    if pw and pre_ptr is None and _pws_ok(Cin, Cout, H * W, xbs, ybs, x_ptr, y_ptr):
+        return "pw_small_kernel", None   # 1x1 with <= 16 channels on one side (the 3/12-channel layers at 256^2)
+    if (_pglast_ok(Cout, Cin, KH, KW, stride, pad, H, W, w_dim, w_contig) and act is None and pre_ptr is None
+            and xact is None):
+        return "pglast_kernel", None     # PatchGAN head 256 -> 1, 4x4 s1
+    if Cout <= 8 and act is None and pre_ptr is None and xact is None:
+        return "small_out_kernel", None  # few output channels (G head, PatchGAN last layer): direct conv
+    if Cin * KH * KW <= 36 and Cout >= 16 and pre_ptr is None and xact is None and act in (None, "relu", "lrelu"):
+        return "small_in_kernel", None   # few input taps into many channels (VGG conv1_1)
+    if pw and _pw_ok(0, Cout, Cin, H * W, 0, xbs, w_ptr, x_ptr):
+        io = xact is None and _pw_io_ok(Cin, H * W, xbs, ybs, x_ptr, y_ptr, pre_ptr, pbs)
+        return "pwgemm_kernel", "io_ws" if io else "gemm"
+    if pw and pre_ptr is None and xact is None and _pwf_ok(0, Cout, Cin, H * W, 0, xbs, w_ptr, x_ptr):
+        return "pwf32_kernel", None
+    if w_dim == 4 and pre_ptr is None and xact is None and _pconv_ok(Cin, KH, KW, stride):
+        return "pconv_kernel", None
+    if (_is16() and w_dim == 4 and (KH > 1 or KW > 1) and Cin % 32 == 0
+            and pre_ptr is None and not accumulate and xact is None and KH * KW <= 16):
+        return "tconv_kernel", None
+    return "igemm_kernel", None
+
+
+def conv_dgrad_family(Cin, H, W, Cout, KH, KW, stride, pad, Ho, Wo, dybs, dxbs, gbs, dy_ptr, dx_ptr, w_ptr,
+                      gpre_ptr, w_dim, w_contig, act, has_bias, accumulate):
+    pw = KH == 1 and KW == 1 and stride == 1 and pad == 0
+    if (KH == 3 and KW == 3 and stride == 1 and pad == 1 and act is None and not has_bias and gpre_ptr is None
+            and w_contig and _thin3_ok(Cout, H, W, dybs, dxbs, dy_ptr, dx_ptr)):
+        return "thin3_kernel", None
+    if (pw and act is None and not has_bias and _pws_ok(Cout, Cin, H * W, dybs, dxbs, dy_ptr, dx_ptr)
+            and (gpre_ptr is None or (gbs % 4 == 0 and gpre_ptr % 16 == 0))):
+        return "pw_small_kernel", None
+    if (_pglast_ok(Cout, Cin, KH, KW, stride, pad, H, W, w_dim, w_contig) and act is None and not has_bias
+            and gpre_ptr is None):
+        return "pglast_kernel", None
+    if Cin <= 8 and act is None and gpre_ptr is None and stride in (1, 2):
+        return "small_out_kernel", None  # data-grad into a 3/6-channel tensor: direct transposed gather
+    if (Cout * KH * KW <= 27 and KH * KW <= 9 and Cin >= 16 and act is None and gpre_ptr is None and stride == 1
+            and not has_bias):
+        return "small_in_kernel", None   # data-grad out of a 3-channel conv (G head)
+    if pw and not has_bias and act is None and _pw_ok(1, Cin, Cout, H * W, 0, dybs, w_ptr, dy_ptr):
+        io = gpre_ptr is None and Cin % 8 == 0 and _pw_io_ok(Cout, H * W, dybs, dxbs, dy_ptr, dx_ptr)
+        return "pwgemm_kernel", "io_ws" if io else "gemm"
+    if pw and not has_bias and act is None and _pwf_ok(1, Cin, Cout, H * W, 0, dybs, w_ptr, dy_ptr):
+        return "pwf32_kernel", None
+    if w_dim == 4 and stride == 1 and act is None and not has_bias and KH == KW and _pconv_ok(Cout, KH, KW, 1):
+        return "pconv_kernel", None      # stride-1 data-grad = forward conv of dy with the flipped, transposed kernel
+    if (_is16() and w_dim == 4 and stride == 2 and pad == 1 and KH == KW and act is None
+            and H <= 2 * Ho and H > 2 * Ho - 2 and W <= 2 * Wo and W > 2 * Wo - 2 and W % 2 == 0 and dxbs % 2 == 0
+            and (gpre_ptr is None or gbs % 2 == 0) and _lib.load().dsgan_pconvt_supported(Cout, KH, stride, pad)):
+        return "pconvt_kernel", None     # stride-2 data-grad / ConvTranspose: all four output parities in one launch
+    if (_is16() and w_dim == 4 and (KH > 1 or KW > 1) and Cout % 32 == 0
+            and act is None and not accumulate and stride in (1, 2) and KH * KW <= 16):
+        return "tconv_kernel", None
+    return "igemm_kernel", None
+
+
+def conv_wgrad_family(N, Cin, H, W, Cout, KH, KW, stride, pad, dybs, xbs, dy_ptr, x_ptr, w_dim, w_contig,
+                      xact, has_db):
+    pw = KH == 1 and KW == 1 and stride == 1 and pad == 0
+    if (xact is None and KH == 3 and KW == 3 and stride == 1 and pad == 1 and w_contig
+            and _thin3_ok(Cout, H, W, dybs, xbs, dy_ptr, x_ptr)):
+        return "thin3_kernel", None
+    if xact is None and w_contig and _pglast_ok(Cout, Cin, KH, KW, stride, pad, H, W, w_dim, w_contig):
+        return "pglast_kernel", None
+    if xact is None and KH * KW in (1, 9, 16) and (Cout <= 8 or (Cin <= 8 and KH * KW == 1)):
+        return "wgrad_small_kernel", None
+    if pw and _pw_ok(2, Cout, N * H * W, H * W, dybs, xbs, dy_ptr, x_ptr):
+        return "pwgemm_kernel", "gemm"
+    if pw and xact is None and _pwf_ok(2, Cout, N * H * W, H * W, dybs, xbs, dy_ptr, x_ptr):
+        return "pwf32_kernel", None
+    if (xact is None and _is16() and w_contig and pad == 1 and W % 4 == 0
+            and xbs % 4 == 0 and x_ptr % 16 == 0 and _lib.load().dsgan_wconv_supported(Cin, KH, KW, stride)):
+        # "db": the bias grad from the staged dy tiles (no channel-sum pass)
+        return "wconv_kernel", "db" if has_db and WCONV_DB_FOLD else "plain"
+    return "igemm_kernel", None
 
 
 def conv_fwd_raw(x, w, b, stride, pad, act=None, out=None, pre=None, accumulate=False, xact=None):
@@ -481,70 +603,74 @@ def conv_fwd_raw(x, w, b, stride, pad, act=None, out=None, pre=None, accumulate=
     pbs = 0
     if pre is not None:
         pre, pbs = nchw(pre)
-    e0 = IGEMM_TIMER.begin()
-    fam = "igemm_kernel"
-    if (KH == 3 and KW == 3 and stride == 1 and pad == 1 and act is None and pre is None and xact is None
-            and w.is_contiguous() and _thin3_ok(Cout, H, W, ybs, xbs, y, x)):
-        # 3x3 into <= 4 channels at full resolution (the G head): row-strip fp32 stream
-        fam = "thin3_kernel"
-        call("dsgan_thin3_fwd", ptr(x), xbs, ptr(w), ptr(b), ptr(y), ybs, N, Cin, Cout, H, W, int(accumulate),
-             stream())
-    elif KH == 1 and KW == 1 and stride == 1 and pad == 0 and pre is None and _pws_ok(Cin, Cout, H * W, xbs, ybs, x, y):
-        # 1x1 with <= 16 channels on one side (the 3/12-channel layers at 256^2): VALU stream
-        fam = "pw_small_kernel"
-        call("dsgan_pw_small", ptr(x), xbs, ptr(w), Cin, 1, ptr(b), ptr(y), ybs, None, 0, N, Cin, Cout, H * W,
-             ACT[act], ACT[xact], 0, int(accumulate), LRELU_SLOPE, stream())
-    elif _pglast_ok(Cout, Cin, KH, KW, stride, pad, H, W, w) and act is None and pre is None and xact is None:
-        # PatchGAN head 256 -> 1, 4x4 s1 (pglast.hip): channel chunks in LDS, partials summed in order
-        fam = "pglast_kernel"
-        ws = torch.empty(_lib.load().dsgan_pglast_workspace(N, Cin, H, W), device=x.device, dtype=torch.float32)
-        call("dsgan_pglast_fwd", ptr(x), xbs, ptr(w), ptr(b), ptr(y), ybs, N, Cin, H, W, int(accumulate), *wsa(ws),
-             stream())
-    elif Cout <= 8 and act is None and pre is None and xact is None:
-        # few output channels (G head, PatchGAN last layer): direct conv, not a GEMM tile
-        fam = "small_out_kernel"
-        call("dsgan_conv_small_out", ptr(x), xbs, ptr(w), Cin * KH * KW, KH * KW, KW, 1, ptr(b), ptr(y), ybs,
-             N, Cin, Cout, H, W, Ho, Wo, KH, KW, stride, pad, 0, int(accumulate), stream())
-    elif Cin * KH * KW <= 36 and Cout >= 16 and pre is None and xact is None and act in (None, "relu", "lrelu"):
-        # few input taps into many channels (VGG conv1_1): thread-per-pixel exact fp32 dot products
-        fam = "small_in_kernel"
-        call("dsgan_conv_small_in", ptr(x), xbs, ptr(w), Cin * KH * KW, KH * KW, KW, 1, ptr(b), ptr(y), ybs,
-             N, Cin, Cout, H, W, Ho, Wo, KH, KW, stride, pad, 0, ACT[act], LRELU_SLOPE, int(accumulate), stream())
-    elif KH == 1 and KW == 1 and stride == 1 and pad == 0 and _pw_ok(0, Cout, Cin, H * W, 0, xbs, w.data_ptr(), x.data_ptr()):
-        fam = "pwgemm_kernel"
-        if xact is None and _pw_io_ok(Cin, H * W, xbs, ybs, x, y, pre, pbs):
+    fam, form = conv_fwd_family(Cin, H, W, Cout, KH, KW, stride, pad, xbs, ybs, pbs, x.data_ptr(), y.data_ptr(),
+                                w.data_ptr(), None if pre is None else pre.data_ptr(), w.dim(), w.is_contiguous(),
+                                act, xact, accumulate)
+    with _timed(IGEMM_TIMER, _conv_flops(N, Cin, Cout, KH, KW, Ho, Wo), ("fwd", N, Cin, H, W, Cout, KH, stride), fam,
+                _nb(x, w, b, y, pre) + (_nb(y) if accumulate else 0.0)):
+        if fam == "thin3_kernel":     # row-strip fp32 stream
+            call("dsgan_thin3_fwd", ptr(x), xbs, ptr(w), ptr(b), ptr(y), ybs, N, Cin, Cout, H, W, int(accumulate),
+                 stream())
+        elif fam == "pw_small_kernel":   # VALU stream
+            call("dsgan_pw_small", ptr(x), xbs, ptr(w), Cin, 1, ptr(b), ptr(y), ybs, None, 0, N, Cin, Cout, H * W,
+                 ACT[act], ACT[xact], 0, int(accumulate), LRELU_SLOPE, stream())
+        elif fam == "pglast_kernel":     # channel chunks in LDS, partials summed in order
+            call("dsgan_pglast_fwd", ptr(x), xbs, ptr(w), ptr(b), ptr(y), ybs, N, Cin, H, W, int(accumulate),
+                 *wsa(_ws("dsgan_pglast_workspace", N, Cin, H, W, like=x)), stream())
+        elif fam == "small_out_kernel":
+            call("dsgan_conv_small_out", ptr(x), xbs, ptr(w), Cin * KH * KW, KH * KW, KW, 1, ptr(b), ptr(y), ybs,
+                 N, Cin, Cout, H, W, Ho, Wo, KH, KW, stride, pad, 0, int(accumulate), stream())
+        elif fam == "small_in_kernel":   # thread-per-pixel exact fp32 dot products
+            call("dsgan_conv_small_in", ptr(x), xbs, ptr(w), Cin * KH * KW, KH * KW, KW, 1, ptr(b), ptr(y), ybs,
+                 N, Cin, Cout, H, W, Ho, Wo, KH, KW, stride, pad, 0, ACT[act], LRELU_SLOPE, int(accumulate), stream())
+        elif form == "io_ws":
             # the cached 16-bit weight copy instead of converting the fp32 weight tile in every
             # workgroup (the same RNE rounding: the same bits)
             call("dsgan_pw_fwd_io_ws", ptr(bf16_weight(w)), 1, ptr(x), xbs, 0, ptr(y), ybs, 0, ptr(pre), pbs, 0,
                  ptr(b), Cout, Cin, H * W, N, ACT[act], int(accumulate), LRELU_SLOPE,
-                 *wsa(_pw_fd_ws(0, Cout, Cin, H * W, N, x)), stream())
-        else:
+                 *wsa(_ws("dsgan_pw_fd_workspace", 0, Cout, Cin, H * W, N, like=x)), stream())
+        elif fam == "pwgemm_kernel":
             call("dsgan_pw_gemm", 0, ptr(w), 0, ptr(x), xbs, ptr(y), ybs, ptr(b), ptr(pre), pbs, None, 0,
                  Cout, N * H * W, Cin, H * W, N, ACT[act], 0, ACT[xact], int(accumulate), LRELU_SLOPE,
-                 *wsa(_pw_fd_ws(0, Cout, Cin, H * W, N, x)), stream())
-    elif (KH == 1 and KW == 1 and stride == 1 and pad == 0 and pre is None and xact is None
-          and _pwf_ok(0, Cout, Cin, H * W, 0, xbs, w.data_ptr(), x.data_ptr())):
-        fam = "pwf32_kernel"
-        call("dsgan_pw_gemm_f32", 0, ptr(w), 0, ptr(x), xbs, ptr(y), ybs, ptr(b), None, 0, Cout, N * H * W, Cin,
-             H * W, N, ACT[act], 0, int(accumulate), LRELU_SLOPE, None, 0, stream())
-    elif w.dim() == 4 and pre is None and xact is None and _pconv_ok(Cin, KH, KW, stride):
-        fam = "pconv_kernel"
-        _pconv(x, xbs, _wtrans_bf16(w, 0), b, y, ybs, N, Cin, Cout, H, W, Ho, Wo, KH, KW, stride, pad, act,
-               None, 0, None, accumulate)
-    elif (_is16() and w.dim() == 4 and (KH > 1 or KW > 1) and Cin % 32 == 0
-          and pre is None and not accumulate and xact is None and KH * KW <= 16):
-        fam = "tconv_kernel"
-        wt = _wtrans_bf16(w, 0) if Cin % 8 == 0 else _wtrans(w, 0)
-        taps = [(kh - pad, kw - pad) for kh in range(KH) for kw in range(KW)]
-        _tconv(x, xbs, wt, b, y, ybs, None, 0, N, Cin, Cout, H, W, Ho, Wo, stride, taps, Ho, Wo, 1, 0, 0,
-               act, None)
-    else:
-        call("dsgan_conv_fwd", ptr(x), xbs, ptr(w), ptr(b), ptr(y), ybs, ptr(pre), pbs, N, Cin, H, W,
-             Cout, KH, KW, stride, pad, Ho, Wo, ACT[act], LRELU_SLOPE, int(accumulate), ACT[xact], _prec(),
-             stream())
-    IGEMM_TIMER.end(e0, _conv_flops(N, Cin, Cout, KH, KW, Ho, Wo), ("fwd", N, Cin, H, W, Cout, KH, stride), fam,
-                    _nb(x, w, b, y, pre) + (_nb(y) if accumulate else 0.0))
+                 *wsa(_ws("dsgan_pw_fd_workspace", 0, Cout, Cin, H * W, N, like=x)), stream())
+        elif fam == "pwf32_kernel":
+            call("dsgan_pw_gemm_f32", 0, ptr(w), 0, ptr(x), xbs, ptr(y), ybs, ptr(b), None, 0, Cout, N * H * W, Cin,
+                 H * W, N, ACT[act], 0, int(accumulate), LRELU_SLOPE, None, 0, stream())
+        elif fam == "pconv_kernel":
+            _pconv(x, xbs, _wtrans_bf16(w, 0), b, y, ybs, N, Cin, Cout, H, W, Ho, Wo, KH, KW, stride, pad, act,
+                   None, 0, None, accumulate)
+        elif fam == "tconv_kernel":
+            wt = _wtrans_bf16(w, 0) if Cin % 8 == 0 else _wtrans(w, 0)
+            taps = [(kh - pad, kw - pad) for kh in range(KH) for kw in range(KW)]
+            _tconv(x, xbs, wt, b, y, ybs, None, 0, N, Cin, Cout, H, W, Ho, Wo, stride, taps, Ho, Wo, 1, 0, 0,
+                   act, None)
+        else:
+            call("dsgan_conv_fwd", ptr(x), xbs, ptr(w), ptr(b), ptr(y), ybs, ptr(pre), pbs, N, Cin, H, W,
+                 Cout, KH, KW, stride, pad, Ho, Wo, ACT[act], LRELU_SLOPE, int(accumulate), ACT[xact], _prec(),
+                 stream())
     return y
+
+
+def _tconv_dgrad(dy, dybs, w, bias, dx, dxbs, gpre, gbs, N, Cin, H, W, Cout, KH, KW, Ho, Wo, stride, pad, gact):
+    """Tap-major data-grad: one launch at stride 1 (flipped kernel), one per output parity at stride 2."""
+    if stride == 1:
+        pp, qq = KH - 1 - pad, KW - 1 - pad
+        taps = [(kh - pp, kw - qq) for kh in range(KH) for kw in range(KW)]
+        _tconv(dy, dybs, _wtrans(w, 1), bias, dx, dxbs, gpre, gbs, N, Cout, Cin, Ho, Wo, H, W, 1, taps, H, W, 1,
+               0, 0, None, gact)
+        return
+    for ph in range(2):
+        for pw_ in range(2):
+            kh0, kw0 = (ph + pad) & 1, (pw_ + pad) & 1
+            nth, ntw = (KH - kh0 + 1) // 2, (KW - kw0 + 1) // 2
+            Hc, Wc = (H - ph + 1) // 2, (W - pw_ + 1) // 2
+            if Hc <= 0 or Wc <= 0:
+                continue
+            ch, cw = (ph + pad - kh0) // 2, (pw_ + pad - kw0) // 2
+            wt = _wtrans(w, 2, kh0, kw0, nth, ntw)
+            taps = [(ch - (nth - 1) + a, cw - (ntw - 1) + c) for a in range(nth) for c in range(ntw)]
+            _tconv(dy, dybs, wt, bias, dx, dxbs, gpre, gbs, N, Cout, Cin, Ho, Wo, Hc, Wc, 1, taps,
+                   H, W, 2, ph, pw_, None, gact)
 
 
 def conv_dgrad_raw(dy, w, x_shape, stride, pad, bias=None, act=None, gpre=None, gact=None,
@@ -559,152 +685,95 @@ def conv_dgrad_raw(dy, w, x_shape, stride, pad, bias=None, act=None, gpre=None, 
     gbs = 0
     if gpre is not None:
         gpre, gbs = nchw(gpre)
-    e0 = IGEMM_TIMER.begin()
-    fam = "igemm_kernel"
-    if (KH == 3 and KW == 3 and stride == 1 and pad == 1 and act is None and bias is None and gpre is None
-            and w.is_contiguous() and _thin3_ok(Cout, H, W, dybs, dxbs, dy, dx)):
-        fam = "thin3_kernel"
-        call("dsgan_thin3_dgrad", ptr(dy), dybs, ptr(w), ptr(dx), dxbs, N, Cin, Cout, H, W, int(accumulate), stream())
-    elif (KH == 1 and KW == 1 and stride == 1 and pad == 0 and act is None and bias is None
-            and _pws_ok(Cout, Cin, H * W, dybs, dxbs, dy, dx) and (gpre is None or (gbs % 4 == 0 and gpre.data_ptr() % 16 == 0))):
-        fam = "pw_small_kernel"
-        call("dsgan_pw_small", ptr(dy), dybs, ptr(w), 1, Cin, None, ptr(dx), dxbs, ptr(gpre), gbs, N, Cout, Cin, H * W,
-             0, 0, ACT[gact], int(accumulate), LRELU_SLOPE, stream())
-    elif _pglast_ok(Cout, Cin, KH, KW, stride, pad, H, W, w) and act is None and bias is None and gpre is None:
-        fam = "pglast_kernel"
-        call("dsgan_pglast_dgrad", ptr(dy), dybs, ptr(w), ptr(dx), dxbs, N, Cin, H, W, int(accumulate), stream())
-    elif Cin <= 8 and act is None and gpre is None and stride in (1, 2):
-        fam = "small_out_kernel"
-        # data-grad into a 3/6-channel tensor: direct transposed gather, w(m=ci, k=co, kh, kw)
-        call("dsgan_conv_small_out", ptr(dy), dybs, ptr(w), KH * KW, Cin * KH * KW, KW, 1, ptr(bias),
-             ptr(dx), dxbs, N, Cout, Cin, Ho, Wo, H, W, KH, KW, stride, pad, 1, int(accumulate), stream())
-    elif Cout * KH * KW <= 27 and KH * KW <= 9 and Cin >= 16 and act is None and gpre is None and stride == 1 and bias is None:
-        # data-grad out of a 3-channel conv (G head): stride-1 transposed gather, w(m=ci, k=co, kh, kw)
-        fam = "small_in_kernel"
-        call("dsgan_conv_small_in", ptr(dy), dybs, ptr(w), KH * KW, Cin * KH * KW, KW, 1, None, ptr(dx), dxbs,
-             N, Cout, Cin, Ho, Wo, H, W, KH, KW, 1, pad, 1, 0, LRELU_SLOPE, int(accumulate), stream())
-    elif (KH == 1 and KW == 1 and stride == 1 and pad == 0 and bias is None and act is None
-            and _pw_ok(1, Cin, Cout, H * W, 0, dybs, w.data_ptr(), dy.data_ptr())):
-        fam = "pwgemm_kernel"
-        if gpre is None and Cin % 8 == 0 and _pw_io_ok(Cout, H * W, dybs, dxbs, dy, dx):
+    fam, form = conv_dgrad_family(Cin, H, W, Cout, KH, KW, stride, pad, Ho, Wo, dybs, dxbs, gbs, dy.data_ptr(),
+                                  dx.data_ptr(), w.data_ptr(), None if gpre is None else gpre.data_ptr(), w.dim(),
+                                  w.is_contiguous(), act, bias is not None, accumulate)
+    with _timed(IGEMM_TIMER, _conv_flops(N, Cin, Cout, KH, KW, Ho, Wo), ("dgrad", N, Cin, H, W, Cout, KH, stride), fam,
+                _nb(dy, w, bias, dx, gpre) + (_nb(dx) if accumulate else 0.0)):
+        if fam == "thin3_kernel":
+            call("dsgan_thin3_dgrad", ptr(dy), dybs, ptr(w), ptr(dx), dxbs, N, Cin, Cout, H, W, int(accumulate),
+                 stream())
+        elif fam == "pw_small_kernel":
+            call("dsgan_pw_small", ptr(dy), dybs, ptr(w), 1, Cin, None, ptr(dx), dxbs, ptr(gpre), gbs, N, Cout, Cin,
+                 H * W, 0, 0, ACT[gact], int(accumulate), LRELU_SLOPE, stream())
+        elif fam == "pglast_kernel":
+            call("dsgan_pglast_dgrad", ptr(dy), dybs, ptr(w), ptr(dx), dxbs, N, Cin, H, W, int(accumulate), stream())
+        elif fam == "small_out_kernel":   # w(m=ci, k=co, kh, kw)
+            call("dsgan_conv_small_out", ptr(dy), dybs, ptr(w), KH * KW, Cin * KH * KW, KW, 1, ptr(bias),
+                 ptr(dx), dxbs, N, Cout, Cin, Ho, Wo, H, W, KH, KW, stride, pad, 1, int(accumulate), stream())
+        elif fam == "small_in_kernel":    # stride-1 transposed gather, w(m=ci, k=co, kh, kw)
+            call("dsgan_conv_small_in", ptr(dy), dybs, ptr(w), KH * KW, Cin * KH * KW, KW, 1, None, ptr(dx), dxbs,
+                 N, Cout, Cin, Ho, Wo, H, W, KH, KW, 1, pad, 1, 0, LRELU_SLOPE, int(accumulate), stream())
+        elif form == "io_ws":
             call("dsgan_pw_dgrad_io_ws", ptr(bf16_weight(w)), 1, ptr(dy), dybs, 0, ptr(dx), dxbs, 0, None, 0, Cin,
-                 Cout, H * W, N, int(accumulate), *wsa(_pw_fd_ws(1, Cin, Cout, H * W, N, dy)), stream())
-        else:
+                 Cout, H * W, N, int(accumulate),
+                 *wsa(_ws("dsgan_pw_fd_workspace", 1, Cin, Cout, H * W, N, like=dy)), stream())
+        elif fam == "pwgemm_kernel":
             call("dsgan_pw_gemm", 1, ptr(w), 0, ptr(dy), dybs, ptr(dx), dxbs, None, None, 0, ptr(gpre), gbs,
                  Cin, N * H * W, Cout, H * W, N, 0, ACT[gact], 0, int(accumulate), LRELU_SLOPE,
-                 *wsa(_pw_fd_ws(1, Cin, Cout, H * W, N, dy)), stream())
-    elif (KH == 1 and KW == 1 and stride == 1 and pad == 0 and bias is None and act is None
-            and _pwf_ok(1, Cin, Cout, H * W, 0, dybs, w.data_ptr(), dy.data_ptr())):
-        fam = "pwf32_kernel"
-        call("dsgan_pw_gemm_f32", 1, ptr(w), 0, ptr(dy), dybs, ptr(dx), dxbs, None, ptr(gpre), gbs, Cin, N * H * W,
-             Cout, H * W, N, 0, ACT[gact], int(accumulate), LRELU_SLOPE, None, 0, stream())
-    elif (w.dim() == 4 and stride == 1 and act is None and bias is None and KH == KW
-          and _pconv_ok(Cout, KH, KW, 1)):
-        # stride-1 data-grad = forward conv of dy with the flipped, transposed kernel
-        fam = "pconv_kernel"
-        _pconv(dy, dybs, _wtrans_bf16(w, 1), None, dx, dxbs, N, Cout, Cin, Ho, Wo, H, W, KH, KW, 1,
-               KH - 1 - pad, None, gpre, gbs, gact, accumulate)
-    elif (_is16() and w.dim() == 4 and stride == 2 and pad == 1 and KH == KW and act is None
-          and H <= 2 * Ho and H > 2 * Ho - 2 and W <= 2 * Wo and W > 2 * Wo - 2 and W % 2 == 0 and dxbs % 2 == 0
-          and (gpre is None or gbs % 2 == 0) and _lib.load().dsgan_pconvt_supported(Cout, KH, stride, pad)):
-        # stride-2 data-grad / ConvTranspose: all four output parities in one launch
-        fam = "pconvt_kernel"
-        call("dsgan_pconvt", ptr(dy), dybs, ptr(_wtrans_bf16(w, 2)), ptr(bias), ptr(dx), dxbs, ptr(gpre), gbs, N,
-             Cout, Cin, Ho, Wo, H, W, KH, stride, pad, ACT[gact], LRELU_SLOPE, int(accumulate), stream())
-    elif (_is16() and w.dim() == 4 and (KH > 1 or KW > 1) and Cout % 32 == 0
-          and act is None and not accumulate and stride in (1, 2) and KH * KW <= 16):
-        fam = "tconv_kernel"
-        if stride == 1:
-            wt = _wtrans(w, 1)
-            pp = KH - 1 - pad
-            qq = KW - 1 - pad
-            taps = [(kh - pp, kw - qq) for kh in range(KH) for kw in range(KW)]
-            _tconv(dy, dybs, wt, bias, dx, dxbs, gpre, gbs, N, Cout, Cin, Ho, Wo, H, W, 1, taps, H, W, 1,
-                   0, 0, None, gact)
+                 *wsa(_ws("dsgan_pw_fd_workspace", 1, Cin, Cout, H * W, N, like=dy)), stream())
+        elif fam == "pwf32_kernel":
+            call("dsgan_pw_gemm_f32", 1, ptr(w), 0, ptr(dy), dybs, ptr(dx), dxbs, None, ptr(gpre), gbs, Cin,
+                 N * H * W, Cout, H * W, N, 0, ACT[gact], int(accumulate), LRELU_SLOPE, None, 0, stream())
+        elif fam == "pconv_kernel":
+            _pconv(dy, dybs, _wtrans_bf16(w, 1), None, dx, dxbs, N, Cout, Cin, Ho, Wo, H, W, KH, KW, 1,
+                   KH - 1 - pad, None, gpre, gbs, gact, accumulate)
+        elif fam == "pconvt_kernel":
+            call("dsgan_pconvt", ptr(dy), dybs, ptr(_wtrans_bf16(w, 2)), ptr(bias), ptr(dx), dxbs, ptr(gpre), gbs, N,
+                 Cout, Cin, Ho, Wo, H, W, KH, stride, pad, ACT[gact], LRELU_SLOPE, int(accumulate), stream())
+        elif fam == "tconv_kernel":
+            _tconv_dgrad(dy, dybs, w, bias, dx, dxbs, gpre, gbs, N, Cin, H, W, Cout, KH, KW, Ho, Wo, stride, pad, gact)
         else:
-            for ph in range(2):
-                for pw_ in range(2):
-                    kh0, kw0 = (ph + pad) & 1, (pw_ + pad) & 1
-                    nth, ntw = (KH - kh0 + 1) // 2, (KW - kw0 + 1) // 2
-                    Hc, Wc = (H - ph + 1) // 2, (W - pw_ + 1) // 2
-                    if Hc <= 0 or Wc <= 0:
-                        continue
-                    ch, cw = (ph + pad - kh0) // 2, (pw_ + pad - kw0) // 2
-                    wt = _wtrans(w, 2, kh0, kw0, nth, ntw)
-                    taps = [(ch - (nth - 1) + a, cw - (ntw - 1) + c) for a in range(nth) for c in range(ntw)]
-                    _tconv(dy, dybs, wt, bias, dx, dxbs, gpre, gbs, N, Cout, Cin, Ho, Wo, Hc, Wc, 1, taps,
-                           H, W, 2, ph, pw_, None, gact)
-    else:
-        call("dsgan_conv_dgrad", ptr(dy), dybs, ptr(w), ptr(bias), ptr(dx), dxbs, None, 0, ptr(gpre), gbs,
-             ACT[gact], N, Cin, H, W, Cout, KH, KW, stride, pad, Ho, Wo, ACT[act], LRELU_SLOPE,
-             int(accumulate), _prec(), stream())
-    IGEMM_TIMER.end(e0, _conv_flops(N, Cin, Cout, KH, KW, Ho, Wo), ("dgrad", N, Cin, H, W, Cout, KH, stride), fam,
-                    _nb(dy, w, bias, dx, gpre) + (_nb(dx) if accumulate else 0.0))
+            call("dsgan_conv_dgrad", ptr(dy), dybs, ptr(w), ptr(bias), ptr(dx), dxbs, None, 0, ptr(gpre), gbs,
+                 ACT[gact], N, Cin, H, W, Cout, KH, KW, stride, pad, Ho, Wo, ACT[act], LRELU_SLOPE,
+                 int(accumulate), _prec(), stream())
     return dx
 
 
 def conv_wgrad_raw(dy, x, dw, stride, pad, xact=None, db=None):
     """dw += conv weight-grad; db (optional) += the bias grad sum(dy) when the kernel taken can fold
     it into the weight-grad (the bf16 pointwise path).  Returns True when db was accumulated."""
-    did_db = False
     dy, dybs = nchw(dy)
     x, xbs = nchw(x)
     N, Cin, H, W = x.shape
-    Cout = dy.shape[1]
+    Cout, Ho, Wo = dy.shape[1], dy.shape[2], dy.shape[3]
     KH, KW = (dw.shape[2], dw.shape[3]) if dw.dim() == 4 else (1, 1)
-    e0 = IGEMM_TIMER.begin()
-    fam = "igemm_kernel"
-    if (xact is None and KH == 3 and KW == 3 and stride == 1 and pad == 1 and dw.is_contiguous()
-            and _thin3_ok(Cout, H, W, dybs, xbs, dy, x)):
-        fam = "thin3_kernel"
-        ws = torch.empty(_lib.load().dsgan_thin3_wgrad_workspace(N, Cin, Cout, H, W), device=dy.device,
-                         dtype=torch.float32)
-        call("dsgan_thin3_wgrad", ptr(dy), dybs, ptr(x), xbs, ptr(dw), *wsa(ws), N, Cin, Cout, H, W, stream())
-    elif xact is None and dw.is_contiguous() and _pglast_ok(Cout, Cin, KH, KW, stride, pad, H, W, dw):
-        fam = "pglast_kernel"
-        ws = torch.empty(_lib.load().dsgan_pglast_workspace(N, Cin, H, W), device=dy.device, dtype=torch.float32)
-        did_db = db is not None
-        call("dsgan_pglast_wgrad", ptr(dy), dybs, ptr(x), xbs, ptr(dw), ptr(db), N, Cin, H, W, *wsa(ws), stream())
-    elif xact is None and KH * KW in (1, 9, 16) and (Cout <= 8 or (Cin <= 8 and KH * KW == 1)):
-        fam = "wgrad_small_kernel"
-        nws = _lib.load().dsgan_conv_wgrad_small_workspace(N, Cin, Cout, KH, KW, dy.shape[2], dy.shape[3])
-        ws = torch.empty(nws, device=dy.device, dtype=torch.float32) if nws > 0 else None
-        call("dsgan_conv_wgrad_small", ptr(dy), dybs, ptr(x), xbs, ptr(dw), N, Cin, H, W, Cout, KH, KW,
-             stride, pad, dy.shape[2], dy.shape[3], *wsa(ws), stream())
-    elif KH == 1 and KW == 1 and stride == 1 and pad == 0 and _pw_ok(2, Cout, N * H * W, H * W, dybs, xbs, dy.data_ptr(), x.data_ptr()):
-        fam = "pwgemm_kernel"
-        did_db = db is not None
-        call("dsgan_pw_gemm", 2, ptr(dy), dybs, ptr(x), xbs, ptr(dw), 0, ptr(db), None, 0, None, 0,
-             Cout, Cin, N * H * W, H * W, N, 0, 0, ACT[xact], 0, LRELU_SLOPE, *wsa(_pw_ws(Cout, Cin, H * W, N, dy)),
-             stream())
-    elif (KH == 1 and KW == 1 and stride == 1 and pad == 0 and xact is None
-          and _pwf_ok(2, Cout, N * H * W, H * W, dybs, xbs, dy.data_ptr(), x.data_ptr())):
-        fam = "pwf32_kernel"
-        nws = _lib.load().dsgan_pw_f32_wgrad_workspace(Cout, Cin, H * W, N)
-        ws = torch.empty(nws, device=dy.device, dtype=torch.float32) if nws > 0 else None
-        did_db = db is not None
-        call("dsgan_pw_gemm_f32", 2, ptr(dy), dybs, ptr(x), xbs, ptr(dw), 0, ptr(db), None, 0, Cout, Cin, N * H * W,
-             H * W, N, 0, 0, 0, LRELU_SLOPE, *wsa(ws), stream())
-    elif (xact is None and _is16() and dw.is_contiguous() and pad == 1 and W % 4 == 0
-          and xbs % 4 == 0 and x.data_ptr() % 16 == 0 and _lib.load().dsgan_wconv_supported(Cin, KH, KW, stride)):
-        fam = "wconv_kernel"
-        Ho, Wo = dy.shape[2], dy.shape[3]
-        ws = torch.empty(_lib.load().dsgan_wconv_workspace(N, Cin, Cout, Ho, Wo, KH, KW), device=dy.device,
-                         dtype=torch.float32)
-        if db is not None and WCONV_DB_FOLD:   # the bias grad from the staged dy tiles (no channel-sum pass)
-            did_db = True
-            call("dsgan_wconv_db", ptr(dy), dybs, ptr(x), xbs, ptr(dw), ptr(db), *wsa(ws), N, Cin, Cout, H, W, Ho, Wo,
-                 KH, KW, stride, pad, stream())
+    fam, form = conv_wgrad_family(N, Cin, H, W, Cout, KH, KW, stride, pad, dybs, xbs, dy.data_ptr(), x.data_ptr(),
+                                  dw.dim(), dw.is_contiguous(), xact, db is not None)
+    # the families whose kernel also sums the bias grad
+    did_db = db is not None and (fam in ("pglast_kernel", "pwgemm_kernel", "pwf32_kernel") or form == "db")
+    with _timed(IGEMM_TIMER, _conv_flops(N, Cin, Cout, KH, KW, Ho, Wo), ("wgrad", N, Cin, H, W, Cout, KH, stride), fam,
+                _nb(dy, x, dw)):
+        if fam == "thin3_kernel":
+            call("dsgan_thin3_wgrad", ptr(dy), dybs, ptr(x), xbs, ptr(dw),
+                 *wsa(_ws("dsgan_thin3_wgrad_workspace", N, Cin, Cout, H, W, like=dy)), N, Cin, Cout, H, W, stream())
+        elif fam == "pglast_kernel":
+            call("dsgan_pglast_wgrad", ptr(dy), dybs, ptr(x), xbs, ptr(dw), ptr(db), N, Cin, H, W,
+                 *wsa(_ws("dsgan_pglast_workspace", N, Cin, H, W, like=dy)), stream())
+        elif fam == "wgrad_small_kernel":
+            call("dsgan_conv_wgrad_small", ptr(dy), dybs, ptr(x), xbs, ptr(dw), N, Cin, H, W, Cout, KH, KW,
+                 stride, pad, Ho, Wo,
+                 *wsa(_ws("dsgan_conv_wgrad_small_workspace", N, Cin, Cout, KH, KW, Ho, Wo, like=dy)), stream())
+        elif fam == "pwgemm_kernel":
+            call("dsgan_pw_gemm", 2, ptr(dy), dybs, ptr(x), xbs, ptr(dw), 0, ptr(db), None, 0, None, 0,
+                 Cout, Cin, N * H * W, H * W, N, 0, 0, ACT[xact], 0, LRELU_SLOPE, *wsa(_pw_ws(Cout, Cin, H * W, N, dy)),
+                 stream())
+        elif fam == "pwf32_kernel":
+            call("dsgan_pw_gemm_f32", 2, ptr(dy), dybs, ptr(x), xbs, ptr(dw), 0, ptr(db), None, 0, Cout, Cin, N * H * W,
+                 H * W, N, 0, 0, 0, LRELU_SLOPE,
+                 *wsa(_ws("dsgan_pw_f32_wgrad_workspace", Cout, Cin, H * W, N, like=dy)), stream())
+        elif fam == "wconv_kernel":
+            ws = _ws("dsgan_wconv_workspace", N, Cin, Cout, Ho, Wo, KH, KW, like=dy)
+            if form == "db":
+                call("dsgan_wconv_db", ptr(dy), dybs, ptr(x), xbs, ptr(dw), ptr(db), *wsa(ws), N, Cin, Cout, H, W, Ho,
+                     Wo, KH, KW, stride, pad, stream())
+            else:
+                call("dsgan_wconv", ptr(dy), dybs, ptr(x), xbs, ptr(dw), *wsa(ws), N, Cin, Cout, H, W, Ho, Wo, KH, KW,
+                     stride, pad, stream())
         else:
-            call("dsgan_wconv", ptr(dy), dybs, ptr(x), xbs, ptr(dw), *wsa(ws), N, Cin, Cout, H, W, Ho, Wo, KH, KW,
-                 stride, pad, stream())
-    else:
-        nws = _lib.load().dsgan_conv_wgrad_workspace(N, Cin, Cout, KH, KW, dy.shape[2], dy.shape[3], _prec())
-        ws = torch.empty(nws, device=dy.device, dtype=torch.float32) if nws > 0 else None
-        call("dsgan_conv_wgrad", ptr(dy), dybs, ptr(x), xbs, ptr(dw), N, Cin, H, W, Cout, KH, KW,
-             stride, pad, dy.shape[2], dy.shape[3], ACT[xact], _prec(), *wsa(ws), stream())
-    IGEMM_TIMER.end(e0, _conv_flops(N, Cin, Cout, KH, KW, dy.shape[2], dy.shape[3]),
-                    ("wgrad", N, Cin, H, W, Cout, KH, stride), fam, _nb(dy, x, dw))
+            call("dsgan_conv_wgrad", ptr(dy), dybs, ptr(x), xbs, ptr(dw), N, Cin, H, W, Cout, KH, KW,
+                 stride, pad, Ho, Wo, ACT[xact], _prec(),
+                 *wsa(_ws("dsgan_conv_wgrad_workspace", N, Cin, Cout, KH, KW, Ho, Wo, _prec(), like=dy)), stream())
     return did_db
 
 
@@ -736,7 +805,6 @@ def zeros(shape, like):
 
 def copy_multi(pairs):
     """dst <- src for a list of (dst, src) dense fp32 tensors of equal size, one launch per 32 pairs."""
-    import ctypes
     if not pairs:
         return
     n = pairs[0][0].numel()
@@ -821,7 +889,6 @@ def _box(t):
 
 
 def _add_n_raw(out, ts):
-    import ctypes
     ts4 = [nchw(t) for t in ts]
     o4, obs = nchw(out)
     N, C, H, W = o4.shape
@@ -969,11 +1036,10 @@ class PatchStemFn(torch.autograd.Function):
         N, Cin, H, W = x.shape
         Cout = w.shape[0]
         y = _empty(N, Cout, H // 2, W // 2, x)
-        e0 = IGEMM_TIMER.begin()
-        call("dsgan_pgstem_fwd", ptr(x), xbs, ptr(w), ptr(b), ptr(y), y[0].numel(), N, Cin, Cout, H, W, LRELU_SLOPE,
-             stream())
-        IGEMM_TIMER.end(e0, _conv_flops(N, Cin, Cout, 4, 4, H // 2, W // 2), ("fwd", N, Cin, H, W, Cout, 4, 2),
-                        "pgstem_kernel", _nb(x, w, b, y))
+        with _timed(IGEMM_TIMER, _conv_flops(N, Cin, Cout, 4, 4, H // 2, W // 2), ("fwd", N, Cin, H, W, Cout, 4, 2),
+                    "pgstem_kernel", _nb(x, w, b, y)):
+            call("dsgan_pgstem_fwd", ptr(x), xbs, ptr(w), ptr(b), ptr(y), y[0].numel(), N, Cin, Cout, H, W,
+                 LRELU_SLOPE, stream())
         ctx.save_for_backward(x, w, b, y)
         ctx.xbs = xbs
         ctx.w_ref, ctx.b_ref = w, b
@@ -995,24 +1061,20 @@ class PatchStemFn(torch.autograd.Function):
             dx4, dxbs = nchw(dx)
             if dx4.data_ptr() != dx.data_ptr():
                 raise RuntimeError("PatchStemFn: accumulation target is not NCHW-dense")
-            e0 = IGEMM_TIMER.begin()
-            call("dsgan_pgstem_dgrad", ptr(dy), dybs, ptr(y), y[0].numel(), ptr(w), ptr(dx), dxbs, N, Cin, Cout, H, W,
-                 LRELU_SLOPE, int(acc), stream())
-            IGEMM_TIMER.end(e0, flops, ("dgrad", N, Cin, H, W, Cout, 4, 2), "pgstem_kernel",
-                            _nb(dy, y, w, dx) + (_nb(dx) if acc else 0.0))
+            with _timed(IGEMM_TIMER, flops, ("dgrad", N, Cin, H, W, Cout, 4, 2), "pgstem_kernel",
+                        _nb(dy, y, w, dx) + (_nb(dx) if acc else 0.0)):
+                call("dsgan_pgstem_dgrad", ptr(dy), dybs, ptr(y), y[0].numel(), ptr(w), ptr(dx), dxbs, N, Cin, Cout,
+                     H, W, LRELU_SLOPE, int(acc), stream())
             dx = None if acc else _give(ctx.box, dx)
         gw = _grad_buf(ctx.w_ref) if ctx.needs_input_grad[1] else None
         gb = _grad_buf(ctx.b_ref) if (b is not None and ctx.needs_input_grad[2]) else None
         if gw is not None or gb is not None:
-            lib = _lib.load()
-            ws = torch.empty(max(lib.dsgan_pgstem_wgrad_workspace(N, Cin, Cout, H, W), 1), device=dy.device,
-                             dtype=torch.float32)
             # a frozen weight with a live bias still runs the weight-grad kernel (into scratch)
             dwt = gw if gw is not None else _keep(torch.zeros_like(w))
-            e0 = IGEMM_TIMER.begin()
-            call("dsgan_pgstem_wgrad", ptr(dy), dybs, ptr(y), y[0].numel(), ptr(x), ctx.xbs, ptr(dwt), ptr(gb), N, Cin,
-                 Cout, H, W, LRELU_SLOPE, *wsa(ws), stream())
-            IGEMM_TIMER.end(e0, flops, ("wgrad", N, Cin, H, W, Cout, 4, 2), "pgstem_kernel", _nb(dy, y, x, dwt))
+            with _timed(IGEMM_TIMER, flops, ("wgrad", N, Cin, H, W, Cout, 4, 2), "pgstem_kernel", _nb(dy, y, x, dwt)):
+                call("dsgan_pgstem_wgrad", ptr(dy), dybs, ptr(y), y[0].numel(), ptr(x), ctx.xbs, ptr(dwt), ptr(gb), N,
+                     Cin, Cout, H, W, LRELU_SLOPE,
+                     *wsa(_ws("dsgan_pgstem_wgrad_workspace", N, Cin, Cout, H, W, like=dy)), stream())
         _params_done(ctx.w_ref, ctx.b_ref)
         return dx, None, None
 
@@ -1069,24 +1131,6 @@ def conv_transpose3s2(x, w, b):
 #   out = Ws x + W2 gelu(W1 h + b1) + b2
 # backward: the dgrad of W2 multiplies by gelu'(z) in its epilogue (no standalone GELU pass).
 # ------------------------------------------------------------------------------------------
-
-_BF16_CACHE = {}
-
-
-def bf16_weight(w):
-    """bf16 copy of a parameter for the fused kernels, cached like _wtrans (same invalidation)."""
-    key = (id(w), w.data_ptr(), tuple(w.shape), half_dtype())
-    ent = _BF16_CACHE.get(key)
-    gen = _wgen(w)
-    if ent is not None and ent[0] == gen and ent[1] == w._version and ent[2] is w:
-        return ent[3]
-    out = torch.empty(w.shape, device=w.device, dtype=half_dtype())
-    call("dsgan_f32_to_bf16", ptr(w), ptr(out), w.numel(), stream())
-    if len(_BF16_CACHE) > 8192:
-        _BF16_CACHE.clear()
-    _BF16_CACHE[key] = (gen, w._version, w, out)
-    return out
-
 
 def _mlp_tile(C, P, HW, x):
     """Pixels per b1-grad partial row of the fused MLP kernels (mlp.hip), 0 if unsupported."""
@@ -1154,10 +1198,9 @@ class PwMlpFn(torch.autograd.Function):
                 mean = torch.empty(N * C, device=d.device, dtype=torch.float32)
                 rstd = torch.empty(N * C, device=d.device, dtype=torch.float32)
                 h = torch.empty((N, C, H, W), device=d.device, dtype=half_dtype())
-                e0 = AUX_TIMER.begin()
-                call("dsgan_instnorm_fwd_bf16", ptr(d), dbs, ptr(h), C * HW, ptr(mean), ptr(rstd), N, C, HW, IN_EPS,
-                     stream())
-                AUX_TIMER.end(e0, 0.0, ("in_fwd_bf16", N, C, H, W), "instnorm", _nb(d, h))
+                with _timed(AUX_TIMER, 0.0, ("in_fwd_bf16", N, C, H, W), "instnorm", _nb(d, h)):
+                    call("dsgan_instnorm_fwd_bf16", ptr(d), dbs, ptr(h), C * HW, ptr(mean), ptr(rstd), N, C, HW,
+                         IN_EPS, stream())
             else:
                 h, mean, rstd = instnorm_raw(d)
                 tile = tile if h.data_ptr() % 16 == 0 else 0
@@ -1168,24 +1211,26 @@ class PwMlpFn(torch.autograd.Function):
         hb = int(h.dtype != torch.float32)
         ctx.hb = hb
         ctx.tile = tile
-        if tile and MLP_FOLD_SC[0]:
-            x4, xbs = nchw(x)
-            if x4.data_ptr() % 16 == 0 and xbs % 4 == 0 and ws.is_contiguous():
-                out = out0 if out0 is not None else _empty(N, P, H, W, h)
-                e0 = IGEMM_TIMER.begin()
-                call("dsgan_mlp_fwd_sc", ptr(h), hbs, hb, ptr(bf16_weight(w1)), ptr(b1), ptr(bf16_weight(w2)), ptr(b2),
-                     ptr(x4), xbs, ptr(bf16_weight(ws)), ptr(out), obs, N, C, P, HW, int(acc1), stream())
-                IGEMM_TIMER.end(e0, _mlp_flops(N, C, P, HW) + 2.0 * N * HW * C * P, ("mlp_fwd", N, C, H, W, P, 1, 1),
-                                "mlp_fwd_kernel", _nb(h, w1, b1, w2, b2, x4, ws) + (2 if acc1 else 1) * _nb(out))
-                ctx.save_for_backward(h, x, ws)
-                return acc if acc1 else out
         if tile:
-            out = conv_fwd_raw(x, ws, None, 1, 0, out=out0, accumulate=acc1)
-            e0 = IGEMM_TIMER.begin()
-            call("dsgan_mlp_fwd", ptr(h), hbs, hb, ptr(bf16_weight(w1)), ptr(b1), ptr(bf16_weight(w2)), ptr(b2),
-                 ptr(out), obs, N, C, P, HW, 1, stream())
-            IGEMM_TIMER.end(e0, _mlp_flops(N, C, P, HW), ("mlp_fwd", N, C, H, W, P, 1, 1), "mlp_fwd_kernel",
-                            _nb(h, w1, b1, w2, b2) + 2 * _nb(out))
+            # the shortcut folded into the kernel, or the shortcut GEMM and the kernel accumulating on it
+            fold = False
+            if MLP_FOLD_SC[0]:
+                x4, xbs = nchw(x)
+                fold = x4.data_ptr() % 16 == 0 and xbs % 4 == 0 and ws.is_contiguous()
+            if fold:
+                out = out0 if out0 is not None else _empty(N, P, H, W, h)
+                flops = _mlp_flops(N, C, P, HW) + 2.0 * N * HW * C * P
+                nbytes = _nb(h, w1, b1, w2, b2, x4, ws) + (2 if acc1 else 1) * _nb(out)
+            else:
+                out = conv_fwd_raw(x, ws, None, 1, 0, out=out0, accumulate=acc1)
+                flops, nbytes = _mlp_flops(N, C, P, HW), _nb(h, w1, b1, w2, b2) + 2 * _nb(out)
+            with _timed(IGEMM_TIMER, flops, ("mlp_fwd", N, C, H, W, P, 1, 1), "mlp_fwd_kernel", nbytes):
+                mlp = (ptr(h), hbs, hb, ptr(bf16_weight(w1)), ptr(b1), ptr(bf16_weight(w2)), ptr(b2))
+                if fold:
+                    call("dsgan_mlp_fwd_sc", *mlp, ptr(x4), xbs, ptr(bf16_weight(ws)), ptr(out), obs, N, C, P, HW,
+                         int(acc1), stream())
+                else:
+                    call("dsgan_mlp_fwd", *mlp, ptr(out), obs, N, C, P, HW, 1, stream())
             ctx.save_for_backward(h, x, ws)
             return acc if acc1 else out
         w1v = w1.view(w1.shape[0], w1.shape[1], 1, 1)
@@ -1196,31 +1241,30 @@ class PwMlpFn(torch.autograd.Function):
             # bf16; pwconv2 and the W2 weight-grad stream g, the pwconv2 data-grad multiplies by gp
             gp = torch.empty((N, C4, H, W), device=h.device, dtype=half_dtype())   # gelu'(z), for dz
             g = torch.empty((N, C4, H, W), device=h.device, dtype=half_dtype())    # gelu(z)
-            e0 = IGEMM_TIMER.begin()
-            call("dsgan_pw_fwd_io_ws", ptr(bf16_weight(w1)), 1, ptr(h), hbs, hb, ptr(g), C4 * HW, 1, ptr(gp), C4 * HW, 1,
-                 ptr(b1), C4, C, HW, N, ACT["gelu"], 0, LRELU_SLOPE, *wsa(_pw_fd_ws(0, C4, C, HW, N, h)), stream())
-            IGEMM_TIMER.end(e0, 2.0 * N * HW * C4 * C, ("fwd", N, C, H, W, C4, 1, 1), "pwgemm_kernel",
-                            _nb(h, w1, b1, g, gp))
+            with _timed(IGEMM_TIMER, 2.0 * N * HW * C4 * C, ("fwd", N, C, H, W, C4, 1, 1), "pwgemm_kernel",
+                        _nb(h, w1, b1, g, gp)):
+                call("dsgan_pw_fwd_io_ws", ptr(bf16_weight(w1)), 1, ptr(h), hbs, hb, ptr(g), C4 * HW, 1, ptr(gp),
+                     C4 * HW, 1, ptr(b1), C4, C, HW, N, ACT["gelu"], 0, LRELU_SLOPE,
+                     *wsa(_ws("dsgan_pw_fd_workspace", 0, C4, C, HW, N, like=h)), stream())
             out = conv_fwd_raw(x, ws, None, 1, 0, out=out0, accumulate=acc1)
-            e0 = IGEMM_TIMER.begin()
-            call("dsgan_pw_fwd_io_ws", ptr(bf16_weight(w2)), 1, ptr(g), C4 * HW, 1, ptr(out), obs, 0, None, 0, 0, ptr(b2),
-                 P, C4, HW, N, 0, 1, LRELU_SLOPE, *wsa(_pw_fd_ws(0, P, C4, HW, N, g)), stream())
-            IGEMM_TIMER.end(e0, 2.0 * N * HW * C4 * P, ("fwd", N, C4, H, W, P, 1, 1), "pwgemm_kernel",
-                            _nb(g, w2, b2) + 2 * _nb(out))
+            with _timed(IGEMM_TIMER, 2.0 * N * HW * C4 * P, ("fwd", N, C4, H, W, P, 1, 1), "pwgemm_kernel",
+                        _nb(g, w2, b2) + 2 * _nb(out)):
+                call("dsgan_pw_fwd_io_ws", ptr(bf16_weight(w2)), 1, ptr(g), C4 * HW, 1, ptr(out), obs, 0, None, 0, 0,
+                     ptr(b2), P, C4, HW, N, 0, 1, LRELU_SLOPE,
+                     *wsa(_ws("dsgan_pw_fd_workspace", 0, P, C4, HW, N, like=g)), stream())
             ctx.g = g
             ctx.save_for_backward(h, x, gp, w1v, w2v, ws)
             return acc if acc1 else out
         z = conv_fwd_raw(h, w1v, b1, 1, 0)
         x4, xbs = nchw(x)
         out = out0 if out0 is not None else _empty(N, P, H, W, h)
-        if 5 * C <= 16 and _pws_ok(5 * C, P, HW, xbs, obs, x4, z) and z.data_ptr() % 16 == 0 \
+        if 5 * C <= 16 and _pws_ok(5 * C, P, HW, xbs, obs, x4.data_ptr(), z.data_ptr()) \
                 and out.data_ptr() % 16 == 0:
             # tiny blocks (c1: 3 -> 12 -> 64 at 256^2): shortcut + pwconv2 in one streaming pass
-            e0 = IGEMM_TIMER.begin()
-            call("dsgan_pw_small2", ptr(x4), xbs, ptr(ws), C, 1, ptr(z), 4 * C * HW, ptr(w2), 4 * C, ptr(b2),
-                 ptr(out), obs, None, 0, N, C, P, HW, 0, ACT["gelu"], 0, int(acc1), LRELU_SLOPE, stream())
-            IGEMM_TIMER.end(e0, 2.0 * N * HW * P * 5 * C, ("fwd", N, 5 * C, H, W, P, 1, 1), "pw_small_kernel",
-                            _nb(x4, z, out, ws, w2, b2))
+            with _timed(IGEMM_TIMER, 2.0 * N * HW * P * 5 * C, ("fwd", N, 5 * C, H, W, P, 1, 1), "pw_small_kernel",
+                        _nb(x4, z, out, ws, w2, b2)):
+                call("dsgan_pw_small2", ptr(x4), xbs, ptr(ws), C, 1, ptr(z), 4 * C * HW, ptr(w2), 4 * C, ptr(b2),
+                     ptr(out), obs, None, 0, N, C, P, HW, 0, ACT["gelu"], 0, int(acc1), LRELU_SLOPE, stream())
         else:
             conv_fwd_raw(x, ws, None, 1, 0, out=out, accumulate=acc1)
             conv_fwd_raw(z, w2v, b2, 1, 0, out=out, accumulate=True, xact="gelu")
@@ -1242,6 +1286,53 @@ class PwMlpFn(torch.autograd.Function):
         dacc = _give(ctx.box_acc, dy, adopt=False) if ctx.needs_input_grad[9] else None
         return _give(ctx.box_h, dh), dx, None, None, None, None, None, None, None, dacc
 
+    # Every backward arm issues, after its data-path kernels: the W2 (or bare b2) grad, the
+    # shortcut's weight-grad, the W1 (or bare b1) grad, then -- _done -- the readiness hook and the
+    # shortcut's data-grad.  The arms differ in which kernel forms the W2 / W1 grads.
+
+    @staticmethod
+    def _b2_sc(dy, x, gb2, gws):
+        """The b2 grad where no weight-grad kernel summed it (gb2 still set), then the shortcut's weight-grad."""
+        if gb2 is not None:
+            channel_sum_raw(dy, gb2)
+        if gws is not None:
+            conv_wgrad_raw(dy, x, gws, 1, 0)
+
+    @staticmethod
+    def _gdz_wgrads(ctx, dy, dybs, g, dz, h, x, grads):
+        """The parameter grads from the 16-bit g = gelu(z) and dz.  The bias grads ride on the
+        weight-grads' staged A tiles (db += sum_k A): b2 from dy, b1 from the bf16 dz (as the fused
+        kernels sum it); a frozen weight with a trainable bias (not on the train path) takes a
+        channel sum instead."""
+        gw2, gb2, gws, gw1, gb1 = grads
+        N, C, H, W = h.shape
+        HW, C4, P = H * W, 4 * C, dy.shape[1]
+        if gw2 is not None:
+            with _timed(IGEMM_TIMER, 2.0 * N * HW * C4 * P, ("wgrad", N, C4, H, W, P, 1, 1), "pwgemm_kernel",
+                        _nb(dy, g, gw2)):
+                call("dsgan_pw_wgrad_mixed", ptr(dy), dybs, 0, ptr(g), C4 * HW, 1, ptr(gw2), ptr(gb2), P, C4, HW, N,
+                     *wsa(_pw_ws(P, C4, HW, N, dy)), stream())
+            gb2 = None
+        PwMlpFn._b2_sc(dy, x, gb2, gws)
+        if gw1 is not None:
+            with _timed(IGEMM_TIMER, 2.0 * N * HW * C4 * C, ("wgrad", N, C, H, W, C4, 1, 1), "pwgemm_kernel",
+                        _nb(dz, h, gw1)):
+                call("dsgan_pw_wgrad_mixed", ptr(dz), C4 * HW, 1, ptr(h), C * HW, ctx.hb, ptr(gw1), ptr(gb1), C4, C,
+                     HW, N, *wsa(_pw_ws(C4, C, HW, N, dz)), stream())
+        elif gb1 is not None:
+            channel_sum_raw(dz.float(), gb1)
+
+    @staticmethod
+    def _done(ctx, dy, ws, x):
+        """Report the parameters' grads launched; returns the shortcut data-grad, accumulated into
+        the shared buffer of x when there is one."""
+        _params_done(*ctx.refs)
+        if not ctx.needs_input_grad[1]:
+            return None
+        out, acc = _acc_target(ctx.box_x)
+        dx = conv_dgrad_raw(dy, ws, tuple(x.shape), 1, 0, out=out, accumulate=acc)
+        return None if acc else _give(ctx.box_x, dx)
+
     @staticmethod
     def _backward_unfused(ctx, dy):
         h, x, z, w1v, w2v, ws = ctx.saved_tensors
@@ -1252,7 +1343,7 @@ class PwMlpFn(torch.autograd.Function):
         if dy.data_ptr() % 16 or dybs % 8:
             dy = dy.contiguous()
             dybs = dy.shape[1] * dy.shape[2] * dy.shape[3]
-        gw2, gb2, gws, gw1, gb1 = (_grad_buf(t) for t in (w2, b2, ws_ref, w1, b1))
+        grads = gw2, gb2, gws, gw1, gb1 = tuple(_grad_buf(t) for t in (w2, b2, ws_ref, w1, b1))
         want_dh = ctx.needs_input_grad[0]
         if ctx.g is not None:
             # bf16 g/gp path (z slot holds gp = gelu'(z)): dz = (W2^T dy) * gp stored bf16, the b1
@@ -1260,65 +1351,30 @@ class PwMlpFn(torch.autograd.Function):
             N, C4, H, W = z.shape
             HW, P, C = H * W, w2.shape[0], h.shape[1]
             dz = torch.empty((N, C4, H, W), device=dy.device, dtype=half_dtype())
-            e0 = IGEMM_TIMER.begin()
-            call("dsgan_pw_dgrad_io_ws", ptr(bf16_weight(w2)), 1, ptr(dy), dybs, 0, ptr(dz), C4 * HW, 1, ptr(z), C4 * HW,
-                 C4, P, HW, N, 0, *wsa(_pw_fd_ws(1, C4, P, HW, N, dy)), stream())
-            IGEMM_TIMER.end(e0, 2.0 * N * HW * C4 * P, ("dgrad", N, C4, H, W, P, 1, 1), "pwgemm_kernel",
-                            _nb(dy, w2, dz, z))
-            # bias grads ride on the weight-grads' staged A tiles (db += sum_k A): b2 from dy, b1 from
-            # the bf16 dz (as the fused kernels sum it)
-            if gw2 is not None:
-                e0 = IGEMM_TIMER.begin()
-                call("dsgan_pw_wgrad_mixed", ptr(dy), dybs, 0, ptr(ctx.g), C4 * HW, 1, ptr(gw2), ptr(gb2), P, C4,
-                     HW, N, *wsa(_pw_ws(P, C4, HW, N, dy)), stream())
-                IGEMM_TIMER.end(e0, 2.0 * N * HW * C4 * P, ("wgrad", N, C4, H, W, P, 1, 1), "pwgemm_kernel",
-                                _nb(dy, ctx.g, gw2))
-            elif gb2 is not None:
-                channel_sum_raw(dy, gb2)
-            if gws is not None:
-                conv_wgrad_raw(dy, x, gws, 1, 0)
-            if gw1 is not None:
-                e0 = IGEMM_TIMER.begin()
-                call("dsgan_pw_wgrad_mixed", ptr(dz), C4 * HW, 1, ptr(h), C * HW, ctx.hb, ptr(gw1), ptr(gb1), C4, C,
-                     HW, N, *wsa(_pw_ws(C4, C, HW, N, dz)), stream())
-                IGEMM_TIMER.end(e0, 2.0 * N * HW * C4 * C, ("wgrad", N, C, H, W, C4, 1, 1), "pwgemm_kernel",
-                                _nb(dz, h, gw1))
-            elif gb1 is not None:   # frozen pwconv1 weight, trainable bias (not on the train path)
-                channel_sum_raw(dz.float(), gb1)
+            with _timed(IGEMM_TIMER, 2.0 * N * HW * C4 * P, ("dgrad", N, C4, H, W, P, 1, 1), "pwgemm_kernel",
+                        _nb(dy, w2, dz, z)):
+                call("dsgan_pw_dgrad_io_ws", ptr(bf16_weight(w2)), 1, ptr(dy), dybs, 0, ptr(dz), C4 * HW, 1, ptr(z),
+                     C4 * HW, C4, P, HW, N, 0, *wsa(_ws("dsgan_pw_fd_workspace", 1, C4, P, HW, N, like=dy)), stream())
+            PwMlpFn._gdz_wgrads(ctx, dy, dybs, ctx.g, dz, h, x, grads)
             dh = None
             if want_dh:
                 dh = _empty(N, C, H, W, dy)
-                e0 = IGEMM_TIMER.begin()
-                call("dsgan_pw_dgrad_io_ws", ptr(bf16_weight(w1)), 1, ptr(dz), C4 * HW, 1, ptr(dh), C * HW, 0, None, 0, C, C4,
-                     HW, N, 0, *wsa(_pw_fd_ws(1, C, C4, HW, N, dz)), stream())
-                IGEMM_TIMER.end(e0, 2.0 * N * HW * C4 * C, ("dgrad", N, C4, H, W, C, 1, 1), "pwgemm_kernel",
-                                _nb(dz, w1, dh))
-            _params_done(*ctx.refs)
-            return dh, PwMlpFn._dx(ctx, dy, ws, x)
+                with _timed(IGEMM_TIMER, 2.0 * N * HW * C4 * C, ("dgrad", N, C4, H, W, C, 1, 1), "pwgemm_kernel",
+                            _nb(dz, w1, dh)):
+                    call("dsgan_pw_dgrad_io_ws", ptr(bf16_weight(w1)), 1, ptr(dz), C4 * HW, 1, ptr(dh), C * HW, 0, None,
+                         0, C, C4, HW, N, 0, *wsa(_ws("dsgan_pw_fd_workspace", 1, C, C4, HW, N, like=dz)), stream())
+            return dh, PwMlpFn._done(ctx, dy, ws, x)
         # fp32 z path: dz = (W2^T dy) * gelu'(z)
         dz = conv_dgrad_raw(dy, w2v, tuple(z.shape), 1, 0, gpre=z, gact="gelu")
         if gw2 is not None and conv_wgrad_raw(dy, z, gw2.view(w2v.shape), 1, 0, xact="gelu", db=gb2):
             gb2 = None
-        if gb2 is not None:
-            channel_sum_raw(dy, gb2)
-        if gws is not None:
-            conv_wgrad_raw(dy, x, gws, 1, 0)
+        PwMlpFn._b2_sc(dy, x, gb2, gws)
         if gw1 is not None and conv_wgrad_raw(dz, h, gw1.view(w1v.shape), 1, 0, db=gb1):
             gb1 = None
         if gb1 is not None:
             channel_sum_raw(dz, gb1)
         dh = conv_dgrad_raw(dz, w1v, tuple(h.shape), 1, 0) if want_dh else None
-        _params_done(*ctx.refs)
-        return dh, PwMlpFn._dx(ctx, dy, ws, x)
-
-    @staticmethod
-    def _dx(ctx, dy, ws, x):
-        """shortcut data-grad, accumulated into the shared buffer of x when there is one"""
-        if not ctx.needs_input_grad[1]:
-            return None
-        out, acc = _acc_target(ctx.box_x)
-        dx = conv_dgrad_raw(dy, ws, tuple(x.shape), 1, 0, out=out, accumulate=acc)
-        return None if acc else _give(ctx.box_x, dx)
+        return dh, PwMlpFn._done(ctx, dy, ws, x)
 
     @staticmethod
     def _backward_fused(ctx, dy):
@@ -1329,7 +1385,7 @@ class PwMlpFn(torch.autograd.Function):
         dy, dybs = nchw(dy)
         if dy.data_ptr() % 16:
             dy, dybs = dy.contiguous(), P * HW
-        gw2, gb2, gws, gw1, gb1 = (_grad_buf(t) for t in (w2, b2, ws_ref, w1, b1))
+        grads = gw2, gb2, gws, gw1, gb1 = tuple(_grad_buf(t) for t in (w2, b2, ws_ref, w1, b1))
         dh = _empty(N, C, H, W, h)
         if gw1 is not None and gb1 is not None and gw2 is not None and C < 256:
             # dh from the data-path kernel; dW1 / db1 / dW2 from the weight-path kernel, which
@@ -1337,51 +1393,25 @@ class PwMlpFn(torch.autograd.Function):
             # are GELU/VALU-bound, so the recompute pays only where the bf16 g/dz round trip is the
             # larger cost: measured at B=16, C=128 @256^2 1.98 -> 1.77 ms, C=256 @128^2 1.70 -> 1.94 ms.)
             w1b, w2b = bf16_weight(w1), bf16_weight(w2)
-            e0 = IGEMM_TIMER.begin()
-            call("dsgan_mlp_bwd", ptr(h), C * HW, ctx.hb, ptr(dy), dybs, ptr(w1b), ptr(b1), ptr(w2b), ptr(dh), C * HW,
-                 None, None, None, N, C, P, HW, stream())
-            IGEMM_TIMER.end(e0, 2.0 * N * HW * C4 * (2 * C + P), ("mlp_bwd", N, C, H, W, P, 1, 1), "mlp_bwd_kernel",
-                            _nb(h, dy, w1, b1, w2, dh))
-            wsp = torch.empty(_lib.load().dsgan_mlp_wgrad_workspace(C, P, HW, N), device=h.device, dtype=torch.float32)
-            e0 = IGEMM_TIMER.begin()
-            call("dsgan_mlp_wgrad", ptr(h), C * HW, ctx.hb, ptr(dy), dybs, ptr(w1b), ptr(b1), ptr(w2b), ptr(gw1),
-                 ptr(gb1), ptr(gw2), *wsa(wsp), N, C, P, HW, stream())
-            IGEMM_TIMER.end(e0, 2.0 * N * HW * C4 * (2 * C + 2 * P), ("mlp_wgrad", N, C, H, W, P, 1, 1),
-                            "mlp_wgrad_kernel", _nb(h, dy, w1, b1, w2, gw1, gb1, gw2))
-            if gb2 is not None:
-                channel_sum_raw(dy, gb2)
-            if gws is not None:
-                conv_wgrad_raw(dy, x, gws, 1, 0)
-            _params_done(*ctx.refs)
-            return dh, PwMlpFn._dx(ctx, dy, ws, x)
+            with _timed(IGEMM_TIMER, 2.0 * N * HW * C4 * (2 * C + P), ("mlp_bwd", N, C, H, W, P, 1, 1),
+                        "mlp_bwd_kernel", _nb(h, dy, w1, b1, w2, dh)):
+                call("dsgan_mlp_bwd", ptr(h), C * HW, ctx.hb, ptr(dy), dybs, ptr(w1b), ptr(b1), ptr(w2b), ptr(dh),
+                     C * HW, None, None, None, N, C, P, HW, stream())
+            with _timed(IGEMM_TIMER, 2.0 * N * HW * C4 * (2 * C + 2 * P), ("mlp_wgrad", N, C, H, W, P, 1, 1),
+                        "mlp_wgrad_kernel", _nb(h, dy, w1, b1, w2, gw1, gb1, gw2)):
+                call("dsgan_mlp_wgrad", ptr(h), C * HW, ctx.hb, ptr(dy), dybs, ptr(w1b), ptr(b1), ptr(w2b), ptr(gw1),
+                     ptr(gb1), ptr(gw2), *wsa(_ws("dsgan_mlp_wgrad_workspace", C, P, HW, N, like=h)), N, C, P, HW,
+                     stream())
+            PwMlpFn._b2_sc(dy, x, gb2, gws)
+            return dh, PwMlpFn._done(ctx, dy, ws, x)
         g = torch.empty((N, C4, H, W), device=h.device, dtype=half_dtype())
         dz = torch.empty_like(g)
-        e0 = IGEMM_TIMER.begin()
-        call("dsgan_mlp_bwd", ptr(h), C * HW, ctx.hb, ptr(dy), dybs, ptr(bf16_weight(w1)), ptr(b1),
-             ptr(bf16_weight(w2)), ptr(dh), C * HW, ptr(g), ptr(dz), None, N, C, P, HW, stream())
-        IGEMM_TIMER.end(e0, _mlp_flops(N, C, P, HW), ("mlp_bwd", N, C, H, W, P, 1, 1), "mlp_bwd_kernel",
-                        _nb(h, dy, w1, b1, w2, dh, g, dz))
-        # bias grads from the weight-grads' staged A tiles: b2 = sum dy, b1 = sum of the bf16 dz
-        if gw2 is not None:
-            e0 = IGEMM_TIMER.begin()
-            call("dsgan_pw_wgrad_mixed", ptr(dy), dybs, 0, ptr(g), C4 * HW, 1, ptr(gw2), ptr(gb2), P, C4, HW, N,
-                 *wsa(_pw_ws(P, C4, HW, N, dy)), stream())
-            IGEMM_TIMER.end(e0, 2.0 * N * HW * C4 * P, ("wgrad", N, C4, H, W, P, 1, 1), "pwgemm_kernel",
-                            _nb(dy, g, gw2))
-        elif gb2 is not None:
-            channel_sum_raw(dy, gb2)
-        if gws is not None:
-            conv_wgrad_raw(dy, x, gws, 1, 0)
-        if gw1 is not None:
-            e0 = IGEMM_TIMER.begin()
-            call("dsgan_pw_wgrad_mixed", ptr(dz), C4 * HW, 1, ptr(h), C * HW, ctx.hb, ptr(gw1), ptr(gb1), C4, C, HW,
-                 N, *wsa(_pw_ws(C4, C, HW, N, dz)), stream())
-            IGEMM_TIMER.end(e0, 2.0 * N * HW * C4 * C, ("wgrad", N, C, H, W, C4, 1, 1), "pwgemm_kernel",
-                            _nb(dz, h, gw1))
-        elif gb1 is not None:
-            channel_sum_raw(dz.float(), gb1)
-        _params_done(*ctx.refs)
-        return dh, PwMlpFn._dx(ctx, dy, ws, x)
+        with _timed(IGEMM_TIMER, _mlp_flops(N, C, P, HW), ("mlp_bwd", N, C, H, W, P, 1, 1), "mlp_bwd_kernel",
+                    _nb(h, dy, w1, b1, w2, dh, g, dz)):
+            call("dsgan_mlp_bwd", ptr(h), C * HW, ctx.hb, ptr(dy), dybs, ptr(bf16_weight(w1)), ptr(b1),
+                 ptr(bf16_weight(w2)), ptr(dh), C * HW, ptr(g), ptr(dz), None, N, C, P, HW, stream())
+        PwMlpFn._gdz_wgrads(ctx, dy, dybs, g, dz, h, x, grads)
+        return dh, PwMlpFn._done(ctx, dy, ws, x)
 
 
 def pw_mlp(h, x, w1, b1, w2, b2, ws, norm=False, slot=None, acc=None):
@@ -1403,11 +1433,10 @@ def dwconv_raw(x, w, b, flip=False, out=None, accumulate=False):
     K = w.shape[-1]
     y = out if out is not None else _empty(N, C, H, W, x)
     y4, ybs = nchw(y)
-    e0 = AUX_TIMER.begin()
-    call("dsgan_dwconv_fwd", ptr(x), xbs, ptr(w), ptr(b), ptr(y4), ybs, N, C, H, W, K, int(flip), int(accumulate),
-         stream())
-    AUX_TIMER.end(e0, 2.0 * N * C * H * W * K * K, ("dw_dgrad" if flip else "dw_fwd", N, C, H, W, K), "dwconv",
-                  (3 if accumulate else 2) * _nb(x))
+    with _timed(AUX_TIMER, 2.0 * N * C * H * W * K * K, ("dw_dgrad" if flip else "dw_fwd", N, C, H, W, K), "dwconv",
+                (3 if accumulate else 2) * _nb(x)):
+        call("dsgan_dwconv_fwd", ptr(x), xbs, ptr(w), ptr(b), ptr(y4), ybs, N, C, H, W, K, int(flip), int(accumulate),
+             stream())
     return y4
 
 
@@ -1416,10 +1445,9 @@ def _dw_wgrad(dy, x, gw, gb, K):
     x4, xbs = nchw(x)
     N, C, H, W = x4.shape
     al = int(x4.data_ptr() % 16 == 0 and dy4.data_ptr() % 16 == 0 and xbs % 4 == 0 and dybs % 4 == 0)
-    ws = torch.empty(_lib.load().dsgan_dwconv_wgrad_workspace(N, C, H, W, K, al), device=x4.device, dtype=torch.float32)
-    e0 = AUX_TIMER.begin()
-    call("dsgan_dwconv_wgrad", ptr(dy4), dybs, ptr(x4), xbs, ptr(gw), ptr(gb), N, C, H, W, K, *wsa(ws), stream())
-    AUX_TIMER.end(e0, 2.0 * N * C * H * W * K * K, ("dw_wgrad", N, C, H, W, K), "dwconv", 2 * _nb(x4))
+    with _timed(AUX_TIMER, 2.0 * N * C * H * W * K * K, ("dw_wgrad", N, C, H, W, K), "dwconv", 2 * _nb(x4)):
+        call("dsgan_dwconv_wgrad", ptr(dy4), dybs, ptr(x4), xbs, ptr(gw), ptr(gb), N, C, H, W, K,
+             *wsa(_ws("dsgan_dwconv_wgrad_workspace", N, C, H, W, K, al, like=x4)), stream())
 
 
 class DwConvFn(torch.autograd.Function):
@@ -1468,11 +1496,10 @@ class MultiDwConvFn(torch.autograd.Function):
         q = C // 4
         y = _empty(N, C, H, W, x4)
         if MultiDwConvFn._multi_ok(x4, xbs, y, C * H * W):
-            e0 = AUX_TIMER.begin()
-            call("dsgan_dwconv_multi_fwd", ptr(x4), xbs, *[ptr(t) for t in wb], ptr(y), C * H * W, N, q, H, W, 0, 0,
-                 stream())
-            AUX_TIMER.end(e0, 2.0 * N * q * H * W * (9 + 25 + 49 + 81), ("dw_multi_fwd", N, C, H, W, 0), "dwconv",
-                          2 * _nb(x4))
+            with _timed(AUX_TIMER, 2.0 * N * q * H * W * (9 + 25 + 49 + 81), ("dw_multi_fwd", N, C, H, W, 0), "dwconv",
+                        2 * _nb(x4)):
+                call("dsgan_dwconv_multi_fwd", ptr(x4), xbs, *[ptr(t) for t in wb], ptr(y), C * H * W, N, q, H, W, 0,
+                     0, stream())
         else:
             for i in range(4):
                 dwconv_raw(x4[:, i * q:(i + 1) * q], wb[2 * i], wb[2 * i + 1], out=y[:, i * q:(i + 1) * q])
@@ -1496,18 +1523,15 @@ class MultiDwConvFn(torch.autograd.Function):
         multi = MultiDwConvFn._multi_ok(x, xbs, dy4, dybs) and (dx is None or dx.stride(0) == C * H * W or N == 1)
         if multi:
             if dx is not None:
-                e0 = AUX_TIMER.begin()
-                call("dsgan_dwconv_multi_fwd", ptr(dy4), dybs, *[ptr(t) if i % 2 == 0 else None for i, t in enumerate(wb)],
-                     ptr(dx), C * H * W, N, q, H, W, 1, int(acc), stream())
-                AUX_TIMER.end(e0, 2.0 * N * q * H * W * 164, ("dw_multi_dgrad", N, C, H, W, 0), "dwconv",
-                              (3 if acc else 2) * _nb(x))
+                with _timed(AUX_TIMER, 2.0 * N * q * H * W * 164, ("dw_multi_dgrad", N, C, H, W, 0), "dwconv",
+                            (3 if acc else 2) * _nb(x)):
+                    call("dsgan_dwconv_multi_fwd", ptr(dy4), dybs,
+                         *[ptr(t) if i % 2 == 0 else None for i, t in enumerate(wb)], ptr(dx), C * H * W, N, q, H, W,
+                         1, int(acc), stream())
             if all(g_ is not None for g_ in grads):
-                wsp = torch.empty(_lib.load().dsgan_dwconv_multi_wgrad_workspace(N, q, H, W), device=x.device,
-                                  dtype=torch.float32)
-                e0 = AUX_TIMER.begin()
-                call("dsgan_dwconv_multi_wgrad", ptr(dy4), dybs, ptr(x), xbs, *[ptr(g_) for g_ in grads], N, q, H, W,
-                     *wsa(wsp), stream())
-                AUX_TIMER.end(e0, 2.0 * N * q * H * W * 164, ("dw_multi_wgrad", N, C, H, W, 0), "dwconv", 2 * _nb(x))
+                with _timed(AUX_TIMER, 2.0 * N * q * H * W * 164, ("dw_multi_wgrad", N, C, H, W, 0), "dwconv", 2 * _nb(x)):
+                    call("dsgan_dwconv_multi_wgrad", ptr(dy4), dybs, ptr(x), xbs, *[ptr(g_) for g_ in grads], N, q, H,
+                         W, *wsa(_ws("dsgan_dwconv_multi_wgrad_workspace", N, q, H, W, like=x)), stream())
                 grads = [None] * 8
         else:
             for i in range(4):
@@ -1532,12 +1556,6 @@ def multi_dwconv(x, w3, b3, w5, b5, w7, b7, w9, b9):
 # InstanceNorm (+scale, +residual, +act)
 # ------------------------------------------------------------------------------------------
 
-def _in_ws(N, C, HW, like):
-    """Scratch of the split InstanceNorm forms (few large planes), None when the shape needs none."""
-    n = _lib.load().dsgan_instnorm_workspace(N, C, HW)
-    return torch.empty(n, device=like.device, dtype=torch.float32) if n > 0 else None
-
-
 def instnorm_raw(x, scale=None, res=None, act=None, out=None):
     x, xbs = nchw(x)
     N, C, H, W = x.shape
@@ -1548,10 +1566,12 @@ def instnorm_raw(x, scale=None, res=None, act=None, out=None):
     y4, ybs = nchw(y)
     mean = torch.empty(N * C, device=x.device, dtype=torch.float32)
     rstd = torch.empty(N * C, device=x.device, dtype=torch.float32)
-    e0 = AUX_TIMER.begin()
-    call("dsgan_instnorm_fwd_ws", ptr(x), xbs, ptr(scale), ptr(res), rbs, ptr(y4), ybs, ptr(mean),
-         ptr(rstd), N, C, H * W, _in_act(act), LRELU_SLOPE, IN_EPS, *wsa(_in_ws(N, C, H * W, x)), stream())
-    AUX_TIMER.end(e0, 0.0, ("in_fwd", N, C, H, W, act, res is not None), "instnorm", (3 if res is not None else 2) * _nb(x))
+    # (scratch: the split forms for few large planes)
+    with _timed(AUX_TIMER, 0.0, ("in_fwd", N, C, H, W, act, res is not None), "instnorm",
+                (3 if res is not None else 2) * _nb(x)):
+        call("dsgan_instnorm_fwd_ws", ptr(x), xbs, ptr(scale), ptr(res), rbs, ptr(y4), ybs, ptr(mean),
+             ptr(rstd), N, C, H * W, _in_act(act), LRELU_SLOPE, IN_EPS,
+             *wsa(_ws("dsgan_instnorm_workspace", N, C, H * W, like=x)), stream())
     return y4, mean, rstd
 
 
@@ -1565,12 +1585,11 @@ def instnorm_bwd_raw(dy, x, scale, res, mean, rstd, act, want_dres, want_dscale)
     dx = _empty(N, C, H, W, x)
     dres = _empty(N, C, H, W, x) if want_dres else None
     dscale = torch.empty(N * C, device=x.device, dtype=torch.float32) if want_dscale else None
-    e0 = AUX_TIMER.begin()
-    call("dsgan_instnorm_bwd_ws", ptr(dy), dybs, ptr(x), xbs, ptr(scale), ptr(res), rbs, ptr(mean),
-         ptr(rstd), ptr(dx), C * H * W, ptr(dres), C * H * W, ptr(dscale), N, C, H * W, _in_act(act),
-         LRELU_SLOPE, IN_EPS, *wsa(_in_ws(N, C, H * W, x)), stream())
-    AUX_TIMER.end(e0, 0.0, ("in_bwd", N, C, H, W, act, res is not None), "instnorm",
-                  (3 + (res is not None) + want_dres) * _nb(x))
+    with _timed(AUX_TIMER, 0.0, ("in_bwd", N, C, H, W, act, res is not None), "instnorm",
+                (3 + (res is not None) + want_dres) * _nb(x)):
+        call("dsgan_instnorm_bwd_ws", ptr(dy), dybs, ptr(x), xbs, ptr(scale), ptr(res), rbs, ptr(mean),
+             ptr(rstd), ptr(dx), C * H * W, ptr(dres), C * H * W, ptr(dscale), N, C, H * W, _in_act(act),
+             LRELU_SLOPE, IN_EPS, *wsa(_ws("dsgan_instnorm_workspace", N, C, H * W, like=x)), stream())
     return dx, dres, dscale
 
 
@@ -1597,6 +1616,18 @@ def instance_norm(x, act=None, res=None):
     return InstanceNormFn.apply(x, res, act)
 
 
+def _instnorm_cat(x, skip, act, slot):
+    """(cat(act(IN(x)), skip), mean, rstd): the IN kernel writes into the first channels of the
+    concatenation; the skip is copied behind them unless it already sits there (``slot``'s tail)."""
+    N, Ca, H, W = x.shape
+    held = slot is not None and slot.holds(skip, Ca)   # the skip's producer already wrote it into the tail
+    out = slot.whole() if held else _empty(N, Ca + skip.shape[1], H, W, x)
+    _, mean, rstd = instnorm_raw(x, None, None, act, out=out[:, :Ca])
+    if not held:
+        copy_into(out[:, Ca:], skip)
+    return out, mean, rstd
+
+
 class InstanceNormCatFn(torch.autograd.Function):
     """cat(act(IN(x)), skip) along channels: the IN kernel writes its plane straight into the
     first Ca channels of the concatenation (upSample, MixConvNeXtML.py:61-66), so only the skip
@@ -1604,15 +1635,8 @@ class InstanceNormCatFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, skip, act, slot=None):
-        N, Ca, H, W = x.shape
-        if slot is not None and slot.holds(skip, Ca):
-            out = slot.whole()   # the skip's producer already wrote it into the tail
-            _, mean, rstd = instnorm_raw(x, None, None, act, out=out[:, :Ca])
-        else:
-            out = _empty(N, Ca + skip.shape[1], H, W, x)
-            _, mean, rstd = instnorm_raw(x, None, None, act, out=out[:, :Ca])
-            copy_into(out[:, Ca:], skip)
-        ctx.act, ctx.Ca = act, Ca
+        out, mean, rstd = _instnorm_cat(x, skip, act, slot)
+        ctx.act, ctx.Ca = act, x.shape[1]
         ctx.save_for_backward(x, mean, rstd)
         ctx.box_x, ctx.box_s = _box(x), _box(skip)
         return out
@@ -1644,13 +1668,7 @@ class ConvTNormFn(torch.autograd.Function):
         Co = w.shape[1]
         t = conv_dgrad_raw(x, w, (N, Co, 2 * Hi, 2 * Wi), 2, 1, bias=b)
         if cat:
-            if slot is not None and slot.holds(other, Co):
-                out = slot.whole()   # the skip's producer already wrote it into the tail
-                _, mean, rstd = instnorm_raw(t, None, None, act, out=out[:, :Co])
-            else:
-                out = _empty(N, Co + other.shape[1], 2 * Hi, 2 * Wi, t)
-                _, mean, rstd = instnorm_raw(t, None, None, act, out=out[:, :Co])
-                copy_into(out[:, Co:], other)
+            out, mean, rstd = _instnorm_cat(t, other, act, slot)
             ctx.save_for_backward(x, w, t, mean, rstd)
         else:
             out, mean, rstd = instnorm_raw(t, None, other, act)
@@ -1667,7 +1685,6 @@ class ConvTNormFn(torch.autograd.Function):
 
     @staticmethod
     def _backward(ctx, dy):
-        import ctypes
         if ctx.cat:
             x, w, t, mean, rstd = ctx.saved_tensors
             res = None
@@ -1685,35 +1702,26 @@ class ConvTNormFn(torch.autograd.Function):
         dres = _empty(N, Co, H, W, t) if want_dres else None
         dth = torch.empty((N, Co, H, W), device=t.device, dtype=half_dtype())
         psum = torch.empty(N * Co, device=t.device, dtype=torch.float32)
-        e0 = AUX_TIMER.begin()
-        call("dsgan_instnorm_bwd_h", ptr(dyt), dybs, ptr(t4), tbs, ptr(res), rbs, ptr(mean), ptr(rstd), ptr(dth),
-             Co * HW, ptr(psum), ptr(dres), Co * HW, N, Co, HW, _in_act(ctx.act), LRELU_SLOPE, IN_EPS, stream())
-        AUX_TIMER.end(e0, 0.0, ("in_bwd_h", N, Co, H, W, ctx.act, res is not None), "instnorm",
-                      _nb(dyt, t4, res, dres) + _nb(dth))
+        with _timed(AUX_TIMER, 0.0, ("in_bwd_h", N, Co, H, W, ctx.act, res is not None), "instnorm",
+                    _nb(dyt, t4, res, dres) + _nb(dth)):
+            call("dsgan_instnorm_bwd_h", ptr(dyt), dybs, ptr(t4), tbs, ptr(res), rbs, ptr(mean), ptr(rstd), ptr(dth),
+                 Co * HW, ptr(psum), ptr(dres), Co * HW, N, Co, HW, _in_act(ctx.act), LRELU_SLOPE, IN_EPS, stream())
         dx = None
         if ctx.needs_input_grad[0]:
             dx = _empty(N, Ci, Hi, Wi, x)
             taps = [(kh - 1, kw - 1) for kh in range(3) for kw in range(3)]
-            dh = (ctypes.c_int * 9)(*[q[0] for q in taps])
-            dw = (ctypes.c_int * 9)(*[q[1] for q in taps])
-            nws = _lib.load().dsgan_tconv_workspace(N, Co, Ci, Hi, Wi, 9)
-            ws = torch.empty(nws, device=t.device, dtype=torch.float32) if nws > 0 else None
-            e0 = IGEMM_TIMER.begin()
-            call("dsgan_tconv_ws_xh", ptr(dth), Co * HW, ptr(_wtrans_bf16(w, 0)), None, ptr(dx), Ci * Hi * Wi, None,
-                 0, N, Co, Ci, H, W, Hi, Wi, 2, 9, ctypes.cast(dh, ctypes.c_void_p), ctypes.cast(dw, ctypes.c_void_p),
-                 Hi, Wi, 1, 0, 0, 0, 0, LRELU_SLOPE, *wsa(ws), stream())
-            IGEMM_TIMER.end(e0, _conv_flops(N, Co, Ci, 3, 3, Hi, Wi), ("fwd", N, Co, H, W, Ci, 3, 2), "tconv_kernel",
-                            _nb(dth, dx) + 2.0 * w.numel())
+            with _timed(IGEMM_TIMER, _conv_flops(N, Co, Ci, 3, 3, Hi, Wi), ("fwd", N, Co, H, W, Ci, 3, 2),
+                        "tconv_kernel", _nb(dth, dx) + 2.0 * w.numel()):
+                _tconv(dth, Co * HW, _wtrans_bf16(w, 0), None, dx, Ci * Hi * Wi, None, 0, N, Co, Ci, H, W, Hi, Wi, 2,
+                       taps, Hi, Wi, 1, 0, 0, None, None, xh=True)
         gw = _grad_buf(ctx.w_ref) if ctx.needs_input_grad[1] else None
         if gw is not None:
             x4, xbs = nchw(x)
-            ws = torch.empty(_lib.load().dsgan_wconv_workspace(N, Co, Ci, Hi, Wi, 3, 3), device=t.device,
-                             dtype=torch.float32)
-            e0 = IGEMM_TIMER.begin()
-            call("dsgan_wconv_xh", ptr(x4), xbs, ptr(dth), Co * HW, ptr(gw), *wsa(ws), N, Co, Ci, H, W, Hi, Wi, 3, 3,
-                 2, 1, stream())
-            IGEMM_TIMER.end(e0, _conv_flops(N, Co, Ci, 3, 3, Hi, Wi), ("wgrad", N, Co, H, W, Ci, 3, 2), "wconv_kernel",
-                            _nb(x4, dth, gw))
+            with _timed(IGEMM_TIMER, _conv_flops(N, Co, Ci, 3, 3, Hi, Wi), ("wgrad", N, Co, H, W, Ci, 3, 2),
+                        "wconv_kernel", _nb(x4, dth, gw)):
+                call("dsgan_wconv_xh", ptr(x4), xbs, ptr(dth), Co * HW, ptr(gw),
+                     *wsa(_ws("dsgan_wconv_workspace", N, Co, Ci, Hi, Wi, 3, 3, like=t)), N, Co, Ci, H, W, Hi, Wi, 3,
+                     3, 2, 1, stream())
         gb = _grad_buf(ctx.b_ref) if (ctx.has_b and ctx.needs_input_grad[2]) else None
         if gb is not None:
             channel_sum_raw(psum.view(N, Co, 1, 1), gb)
@@ -1749,13 +1757,8 @@ def convt_norm(x, w, b, other, act=None, cat=False, slot=None):
 class MaxPoolFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, k):
-        x4, xbs = nchw(x)
-        N, C, H, W = x4.shape
-        Ho, Wo = H // k, W // k
-        y = _empty(N, C, Ho, Wo, x4)
-        idx = torch.empty((N, C, Ho, Wo), device=x4.device, dtype=torch.int32)
-        call("dsgan_maxpool_fwd", ptr(x4), xbs, ptr(y), C * Ho * Wo, ptr(idx), N, C, H, W, k, stream())
-        ctx.k, ctx.shape = k, (N, C, H, W)
+        y, idx = maxpool_raw(x, k)
+        ctx.k, ctx.shape = k, tuple(x.shape)
         ctx.save_for_backward(idx)
         ctx.mark_non_differentiable(idx)
         # (no zero-filled int grad for idx per backward: autograd would materialise one)
@@ -1897,24 +1900,19 @@ def _cb16_empty(N, C, H, W, like, dtype):
 
 def _vgg_wt(w, dgrad):
     """bf16 weights of a VGG conv swizzled into vconv3x3's LDS image (dsgan_vconv_wtrans), cached."""
-    key = (id(w), w.data_ptr(), tuple(w.shape), "vconv", dgrad, half_dtype())
-    ent = _WT_CACHE.get(key)
-    gen = _wgen(w)
-    if ent is not None and ent[0] == gen and ent[1] == w._version and ent[2] is w:
-        return ent[3]
-    Co, Ci = w.shape[0], w.shape[1]
-    wt = torch.empty(_lib.load().dsgan_vconv_wtrans_size(Co, Ci), device=w.device, dtype=half_dtype())
-    call("dsgan_vconv_wtrans", ptr(w), ptr(wt), Co, Ci, int(dgrad), stream())
-    _WT_CACHE[key] = (gen, w._version, w, wt)
-    return wt
+    def build():
+        Co, Ci = w.shape[0], w.shape[1]
+        wt = torch.empty(_lib.load().dsgan_vconv_wtrans_size(Co, Ci), device=w.device, dtype=half_dtype())
+        call("dsgan_vconv_wtrans", ptr(w), ptr(wt), Co, Ci, int(dgrad), stream())
+        return wt
+    return _cached(_WT_CACHE, w, ("vconv", dgrad, half_dtype()), build)
 
 
 def _vconv(x, wt, bias, mask, y, N, K, M, H, W, relu, tag):
-    e0 = IGEMM_TIMER.begin()
-    call("dsgan_vconv3x3", ptr(x), ptr(wt), ptr(bias), ptr(mask), ptr(y), int(y.dtype == torch.float32), int(relu),
-         N, K, M, H, W, stream())
-    IGEMM_TIMER.end(e0, _conv_flops(N, K, M, 3, 3, H, W), (tag, N, K, H, W, M, 3, 1), "vconv_kernel",
-                    _nb(x, wt, bias, mask, y))
+    with _timed(IGEMM_TIMER, _conv_flops(N, K, M, 3, 3, H, W), (tag, N, K, H, W, M, 3, 1), "vconv_kernel",
+                _nb(x, wt, bias, mask, y)):
+        call("dsgan_vconv3x3", ptr(x), ptr(wt), ptr(bias), ptr(mask), ptr(y), int(y.dtype == torch.float32), int(relu),
+             N, K, M, H, W, stream())
     return y
 
 
@@ -1999,7 +1997,6 @@ def _perceptual_bwd_cb16(ctx, g):
 def _sum4_raw(outs):
     """((L1(f1) + L1(f2)) + L1(f3)) + L1(f0) -- the reference's order -- in one dsgan_loss_combine
     launch (the fp32 adds of the three torch adds it replaces)."""
-    import ctypes
     xp = (ctypes.c_void_p * 4)(*[outs[i:].data_ptr() for i in (1, 2, 3, 0)])
     ones, zeros = (ctypes.c_float * 4)(1, 1, 1, 1), (ctypes.c_float * 4)(0, 0, 0, 0)
     out = torch.empty((), device=outs.device, dtype=torch.float32)
@@ -2161,7 +2158,6 @@ class AddNFn(torch.autograd.Function):
         ts = [nchw(t) for t in xs]
         N, C, H, W = ts[0][0].shape
         out = _empty(N, C, H, W, ts[0][0])
-        import ctypes
         arr = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t, _ in ts])
         bss = (ctypes.c_long * len(ts))(*[bs for _, bs in ts])
         call("dsgan_add_n", ctypes.cast(arr, ctypes.c_void_p), ctypes.cast(bss, ctypes.c_void_p), len(ts),
@@ -2311,7 +2307,6 @@ class LossSumFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, coefs, scale, *xs):
-        import ctypes
         n = len(xs)
         fa = ctypes.c_float * n
         ctx.a = fa(*[float(a) for a, _, _ in coefs])
@@ -2327,7 +2322,6 @@ class LossSumFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        import ctypes
         gx = torch.empty(ctx.n, device=g.device, dtype=torch.float32)
         call("dsgan_loss_combine_bwd", ptr(g.contiguous()), ctypes.cast(ctx.a, ctypes.c_void_p),
              ctypes.cast(ctx.c, ctypes.c_void_p), ctx.n, ctx.scale, ptr(gx), stream())
@@ -2412,13 +2406,11 @@ MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
 def ms_ssim_affine(real, fake, a=1.0, b=0.0, data_range=1.0, weights=MS_SSIM_WEIGHTS, size_average=True):
     """MS-SSIM of (a*real+b, a*fake+b) (DSGAN/MS_SSIM.py:153-225), evaluation only (no autograd):
     a 0-d tensor (size_average) or the per-image values [N]."""
-    import ctypes
     real, fake = real.detach().contiguous(), fake.detach().contiguous()
     if real.shape != fake.shape or real.dim() != 4:
         raise ValueError("ms_ssim: two (N,C,H,W) tensors of the same shape required")
     N, C, H, W = real.shape
-    lib = _lib.load()
-    work = torch.empty(lib.dsgan_ms_ssim_workspace(N, C, H, W), device=real.device, dtype=torch.float32)
+    work = _ws("dsgan_ms_ssim_workspace", N, C, H, W, like=real)
     stats = torch.empty(2 * len(weights) * N * C, device=real.device, dtype=torch.float32)
     out = torch.empty(N + 1, device=real.device, dtype=torch.float32)
     wh = (ctypes.c_float * len(weights))(*[float(w) for w in weights])
@@ -2436,14 +2428,12 @@ class MSSSIMFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, real, fake, a, b, data_range, weights):
-        import ctypes
         real, fake = real.contiguous(), fake.contiguous()
         if real.shape != fake.shape or real.dim() != 4:
             raise ValueError("ms_ssim: two (N,C,H,W) tensors of the same shape required")
         N, C, H, W = real.shape
         L = len(weights)
-        lib = _lib.load()
-        work = torch.empty(lib.dsgan_ms_ssim_train_workspace(N, C, H, W, L), device=real.device, dtype=torch.float32)
+        work = _ws("dsgan_ms_ssim_train_workspace", N, C, H, W, L, like=real)
         stats = torch.empty(2 * L * N * C, device=real.device, dtype=torch.float32)
         out = torch.empty(N + 1, device=real.device, dtype=torch.float32)
         wh = (ctypes.c_float * L)(*[float(w) for w in weights])
@@ -2457,7 +2447,6 @@ class MSSSIMFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        import ctypes
         real, fake, work, stats = ctx.saved_tensors
         a, b, C1, C2, weights = ctx.args
         N, C, H, W = real.shape
