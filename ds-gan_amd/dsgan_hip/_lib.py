@@ -81,6 +81,7 @@ SIGNATURES = {
     # pconvt.hip
     "dsgan_pconvt_supported": [I, I, I, I],
     "dsgan_pconvt": [P, L, P, P, P, L, P, L] + [I] * 11 + [F, I, S],
+    "dsgan_pconvt_tune": [I, I],
     # wconv.hip
     "dsgan_wconv_supported": [I, I, I, I],
     "dsgan_wconv_workspace": [I, I, I, I, I, I, I],

@@ -375,6 +375,12 @@ int dsgan_pconvt_supported(int K, int KS, int stride, int pad);
 int dsgan_pconvt(const float* X, long x_bs, const void* Wb, const float* bias, float* Y, long y_bs,
                  const float* gpre, long gpre_bs, int nb, int K, int M, int Hi, int Wi, int Ho, int Wo,
                  int KS, int stride, int pad, int gact, float slope, int accumulate, hipStream_t stream);
+/* planner knob `key` <- val (val < 0: read only), returns the previous value (measurement tools, tests):
+ * key 0 = kernel form, 0 the per-shape rule (default), 1 the LDS-DMA ring wherever its address maps
+ *         allow (16-byte aligned X, x_bs % 4 == 0, Wi % 4 == 0), 2 the register-staged kernel always.
+ *         Both forms give the same bits.
+ * key 1 = (read) the form the last dsgan_pconvt launch took: 0 register-staged, 1 ring. */
+int dsgan_pconvt_tune(int key, int val);
 
 /* ---- patch-staged conv weight-grad (wconv.hip): ConvTranspose2d 3x3/s2 weight-grads
  * (MixConvNeXtML.py:53,149-152, as the equivalent stride-2 conv) and PatchGAN 4x4 s2/s1
