@@ -168,6 +168,14 @@ SIGNATURES = {
     "dsgan_ms_ssim_fwd_train": [P, P, F, F, I, I, I, I, P, F, F, P, I, P, L, P, P, S],
     "dsgan_ms_ssim_bwd": [P, P, F, F, I, I, I, I, P, F, F, P, I, P, L, P, P, P, I, S],
     "dsgan_ssim_bwd": [P, P, F, F, I, I, I, P, P, P, F, P, I, S],
+    # lsgan.hip
+    "dsgan_sigmoid_fwd": [P, L, P, S],
+    "dsgan_sigmoid_bwd": [P, P, L, P, I, S],
+    "dsgan_mse_const_fwd": [P, L, F, P, P, S],
+    "dsgan_mse_const_bwd": [P, L, F, P, P, I, S],
+    "dsgan_avgpool3s2_fast_supported": [P, L, P, L, I, I, I],
+    "dsgan_avgpool3s2_fwd": [P, L, P, L, I, I, I, I, I, S],
+    "dsgan_avgpool3s2_bwd": [P, L, P, L, I, I, I, I, I, I, S],
     # vggconv.hip
     "dsgan_vconv_supported": [I, I, I, I],
     "dsgan_vconv_tune": [I, I],

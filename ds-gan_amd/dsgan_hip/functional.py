@@ -416,14 +416,20 @@ def _refresh_half_copies(params):
 
 
 def _wtrans(w, mode, kh0=0, kw0=0, nth=0, ntw=0):
-    """fp32 tap-major weights for tconv.hip, cached (rebuilt at the next use after an update)."""
-    return _cached(_WT_CACHE, w, (mode, kh0, kw0, nth, ntw), lambda: _wtrans_build(w, mode, kh0, kw0, nth, ntw))
+    """fp32 tap-major weights for tconv.hip, cached (rebuilt at the next use after an update).  The
+    rebuild writes the entry's own buffer: a launch captured into a HIP graph while the entry was
+    current (the D step's data-grads, whose copies the preceding G step rebuilt) keeps reading the
+    buffer that later rebuilds refresh, instead of a copy no replay writes again."""
+    what = (mode, kh0, kw0, nth, ntw)
+    old = _WT_CACHE.get((id(w), w.data_ptr(), tuple(w.shape)) + what)
+    out = old.copy if old is not None and old.w is w else None
+    return _cached(_WT_CACHE, w, what, lambda: _wtrans_build(w, mode, kh0, kw0, nth, ntw, out))
 
 
-def _wtrans_build(w, mode, kh0=0, kw0=0, nth=0, ntw=0):
+def _wtrans_build(w, mode, kh0=0, kw0=0, nth=0, ntw=0, out=None):
     Co, Ci, KH, KW = w.shape
     taps = nth * ntw if mode == 2 else KH * KW
-    wt = torch.empty(taps * Co * Ci, device=w.device, dtype=torch.float32)
+    wt = out if out is not None else torch.empty(taps * Co * Ci, device=w.device, dtype=torch.float32)
     call("dsgan_conv_wtrans", ptr(w), ptr(wt), Co, Ci, KH, KW, mode, kh0, kw0, nth, ntw, stream())
     return wt
 
@@ -2461,3 +2467,112 @@ class MSSSIMFn(torch.autograd.Function):
 def ms_ssim_loss_affine(real, fake, a=0.5, b=0.5, data_range=1.0, weights=MS_SSIM_WEIGHTS):
     """Differentiable batch-mean MS-SSIM of (a*real+b, a*fake+b); gradient w.r.t. fake only."""
     return MSSSIMFn.apply(real, fake, a, b, data_range, tuple(weights))
+
+
+# ------------------------------------------------------------------------------------------
+# LSGAN objective (--no_lsgan, quirk q3) and the multi-scale D's input pyramid (lsgan.hip)
+# ------------------------------------------------------------------------------------------
+
+class SigmoidFn(torch.autograd.Function):
+    """nn.Sigmoid in fp32 with the accurate exp (a loss input, not a gate); the backward reads the
+    saved output, as torch's does."""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = x.contiguous()
+        y = torch.empty_like(x)
+        with _timed(AUX_TIMER, 0.0, ("sigmoid_fwd", x.numel()), "sigmoid", _nb(x, y)):
+            call("dsgan_sigmoid_fwd", ptr(x), x.numel(), ptr(y), stream())
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (y,) = ctx.saved_tensors
+        dy = dy.contiguous()
+        dx = torch.empty_like(y)
+        with _timed(AUX_TIMER, 0.0, ("sigmoid_bwd", y.numel()), "sigmoid", _nb(y, dy, dx)):
+            call("dsgan_sigmoid_bwd", ptr(y), ptr(dy), y.numel(), ptr(dx), 0, stream())
+        return dx
+
+
+def sigmoid(x):
+    return SigmoidFn.apply(x)
+
+
+class MseConstFn(torch.autograd.Function):
+    """mean((x - target)^2) against a constant label (nn.MSELoss of GANLoss / GANLoss_multi)."""
+
+    @staticmethod
+    def forward(ctx, x, target):
+        ctx.box = _box(x)
+        x = x.contiguous()
+        out = torch.empty((), device=x.device, dtype=torch.float32)
+        with _timed(AUX_TIMER, 0.0, ("mse_fwd", x.numel()), "mse_const", _nb(x)):
+            call("dsgan_mse_const_fwd", ptr(x), x.numel(), float(target), ptr(out), ptr(_loss_part(x)), stream())
+        ctx.target = float(target)
+        ctx.save_for_backward(x)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        g = g.contiguous()
+
+        def run(d, acc):
+            with _timed(AUX_TIMER, 0.0, ("mse_bwd", x.numel()), "mse_const", _nb(x, d) + (_nb(d) if acc else 0.0)):
+                call("dsgan_mse_const_bwd", ptr(x), x.numel(), ctx.target, ptr(g), ptr(d), acc, stream())
+        return _loss_grad(ctx.box, x, run), None
+
+
+def mse_const(x, target):
+    return MseConstFn.apply(x, target)
+
+
+# AvgPool2d(3, 2, 1, count_include_pad=False) on the 16-byte form where it applies (off: the scalar
+# form everywhere; tests / A-B -- the two give the same bits)
+AVGPOOL_FAST = [True]
+
+
+def avg_pool3s2_raw(x, out=None):
+    x, xbs = nchw(x)
+    N, C, H, W = x.shape
+    y = out if out is not None else _empty(N, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1, x)
+    y, ybs = nchw(y)
+    with _timed(AUX_TIMER, 0.0, ("avgpool_fwd", N, C, H, W), "avgpool3s2", _nb(x, y)):
+        call("dsgan_avgpool3s2_fwd", ptr(x), xbs, ptr(y), ybs, N, C, H, W, 0 if AVGPOOL_FAST[0] else 1, stream())
+    return y
+
+
+def avg_pool3s2_bwd_raw(dy, x_shape, out=None, accumulate=False):
+    dy, dybs = nchw(dy)
+    N, C, H, W = x_shape
+    dx = out if out is not None else torch.empty((N, C, H, W), device=dy.device, dtype=torch.float32)
+    dx4, dxbs = nchw(dx)
+    if dx4.data_ptr() != dx.data_ptr():
+        raise RuntimeError("avg_pool3s2: gradient target is not NCHW-dense")
+    with _timed(AUX_TIMER, 0.0, ("avgpool_bwd", N, C, H, W), "avgpool3s2", _nb(dy, dx) + (_nb(dx) if accumulate else 0.0)):
+        call("dsgan_avgpool3s2_bwd", ptr(dy), dybs, ptr(dx), dxbs, N, C, H, W, int(accumulate),
+             0 if AVGPOOL_FAST[0] else 1, stream())
+    return dx
+
+
+class AvgPool3s2Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        ctx.box = _box(x)
+        ctx.x_shape = tuple(x.shape)
+        return avg_pool3s2_raw(x)
+
+    @staticmethod
+    def backward(ctx, dy):
+        buf, acc = _acc_target(ctx.box)
+        if acc and buf.dtype == torch.float32 and tuple(buf.shape) == ctx.x_shape and nchw(buf)[0] is buf:
+            avg_pool3s2_bwd_raw(dy, ctx.x_shape, out=buf, accumulate=True)   # a shared input: old + new in-kernel
+            return None
+        return _give(ctx.box, avg_pool3s2_bwd_raw(dy, ctx.x_shape))
+
+
+def avg_pool3s2(x):
+    """AvgPool2d(3, stride=2, padding=1, count_include_pad=False) (MultiscaleDiscriminator.downsample)."""
+    return AvgPool3s2Fn.apply(x)

@@ -1,11 +1,18 @@
-"""Network factory, init, scheduler, GAN loss and the PatchGAN D (DSGAN/models/networks.py).
+"""Network factory, init, scheduler, GAN losses and the discriminators (DSGAN/models/networks.py).
 
 Keeps the reference's string-dispatch surface (``define_G`` / ``define_D``, unknown names raise
-``NotImplementedError``) for the networks on the DS-GAN path: ``MixConvNeXtML`` and the
-``basic`` / ``n_layers`` PatchGAN.  Other reference generators are out of scope (SURVEY.md §2,
-row 6x) and raise the reference's own error.
+``NotImplementedError``) for the networks on the DS-GAN path: ``MixConvNeXtML`` and every
+discriminator ``Pix2PixModel`` can train under ``--norm instance``: the ``basic`` / ``n_layers``
+PatchGAN, the ``pixel`` 1x1 discriminator and the three-scale ``multi`` discriminator, each with or
+without the trailing ``nn.Sigmoid`` (``use_sigmoid``).  Both objectives are here: BCE-with-logits
+(the default) and least squares (``GANLoss(use_lsgan=True)`` / ``GANLoss_multi``), which the
+reference's backwards-wired ``--no_lsgan`` turns ON together with the sigmoid (quirk q3).  ``multi``
+without the sigmoid raises: the reference pairs it with ``BCELoss`` on raw logits, which fails in
+torch itself.  Other reference generators are out of scope and raise the
+reference's own error.
 """
 import functools
+import math
 
 import torch
 import torch.nn as nn
@@ -94,8 +101,8 @@ def define_G(input_nc, output_nc, ngf, which_model_netG, norm="batch", use_dropo
 
 def define_D(input_nc, ndf, which_model_netD, n_layers_D=3, norm="batch", use_sigmoid=False,
              init_type="normal", gpu_ids=()):
-    """DSGAN/models/networks.py:115-131.  The PatchGAN runs InstanceNorm (affine=False, the
-    reference default ``--norm instance``) fused into its conv kernels; ``--norm batch`` (affine
+    """DSGAN/models/networks.py:115-131.  The discriminators run InstanceNorm (affine=False, the
+    reference default ``--norm instance``) fused into their conv kernels; ``--norm batch`` (affine
     BatchNorm2d with running stats) and ``none`` are not on the DS-GAN path and raise instead of
     silently training a different discriminator."""
     if norm != "instance":
@@ -106,32 +113,89 @@ def define_D(input_nc, ndf, which_model_netD, n_layers_D=3, norm="batch", use_si
         netD = NLayerDiscriminator(input_nc, ndf, n_layers=3, norm_layer=norm_layer, use_sigmoid=use_sigmoid)
     elif which_model_netD == "n_layers":
         netD = NLayerDiscriminator(input_nc, ndf, n_layers_D, norm_layer=norm_layer, use_sigmoid=use_sigmoid)
+    elif which_model_netD == "pixel":
+        netD = PixelDiscriminator(input_nc, ndf, norm_layer=norm_layer, use_sigmoid=use_sigmoid)
+    elif which_model_netD == "multi":
+        if not use_sigmoid:
+            raise NotImplementedError(
+                "define_D: [multi] without --no_lsgan is not supported: the reference pairs it with "
+                "GANLoss_multi's nn.BCELoss on raw logits, which fails in the reference itself "
+                "(\"all elements of input should be between 0 and 1\"); pass --no_lsgan (sigmoid + least squares)")
+        netD = MultiscaleDiscriminator(input_nc, ndf, n_layers_D, norm_layer, use_sigmoid, num_D=3, getIntermFeat=False)
     else:
         raise NotImplementedError("Discriminator model name [%s] is not recognized" % which_model_netD)
     return init_net(netD, init_type, gpu_ids)
 
 
+def _fusable(*xs):
+    """Loss terms HF.loss_sum takes: 0-d fp32 device tensors (a disabled term may be a python 0)."""
+    ts = [x for x in xs if not (not torch.is_tensor(x) and x == 0)]
+    return bool(ts) and len(ts) <= 8 and all(torch.is_tensor(x) and x.dim() == 0 and x.dtype == torch.float32
+                                             and x.is_cuda for x in ts)
+
+
 class GANLoss(nn.Module):
     """DSGAN/models/networks.py:143-163.  use_lsgan=False (the default, quirk q3) is
-    BCEWithLogits against a constant label, computed by the fused HIP reduction."""
+    BCEWithLogits against a constant label, use_lsgan=True (``--no_lsgan``) nn.MSELoss against it;
+    both are fused HIP reductions."""
 
     def __init__(self, use_lsgan=True, target_real_label=1.0, target_fake_label=0.0):
         super().__init__()
         self.register_buffer("real_label", torch.tensor(target_real_label))
         self.register_buffer("fake_label", torch.tensor(target_fake_label))
         self.use_lsgan = use_lsgan
-        if use_lsgan:
-            raise NotImplementedError("LSGAN (MSE) GAN loss is not on the DS-GAN path; "
-                                      "the reference default is BCEWithLogits (--no_lsgan unset)")
+        self.labels = (float(target_fake_label), float(target_real_label))
 
     def __call__(self, input, target_is_real):
+        if self.use_lsgan:
+            return HF.mse_const(input, self.labels[1 if target_is_real else 0])
         return HF.bce_with_logits(input, 1.0 if target_is_real else 0.0)
+
+
+class GANLoss_multi(nn.Module):
+    """DSGAN/models/networks.py:166-208: the least-squares loss of the multi-scale D, summed over the
+    scales in list order (``0 + l0 + l1 + l2``).  Takes the D's list of lists (the last entry of each
+    scale is its prediction) or one scale's list."""
+
+    def __init__(self, use_lsgan=True, target_real_label=1.0, target_fake_label=0.0, tensor=None):
+        super().__init__()
+        if not use_lsgan:
+            raise NotImplementedError("GANLoss_multi(use_lsgan=False) is nn.BCELoss on the multi D's output, which "
+                                      "the reference itself cannot train (define_D rejects that pairing)")
+        self.real_label, self.fake_label = float(target_real_label), float(target_fake_label)
+
+    def __call__(self, input, target_is_real):
+        t = self.real_label if target_is_real else self.fake_label
+        if not isinstance(input[0], list):
+            return HF.mse_const(input[-1], t)
+        ls = [HF.mse_const(input_i[-1], t) for input_i in input]
+        if _fusable(*ls):   # one launch each way; 0 + l0 is l0
+            return HF.loss_sum([(l, 1.0) for l in ls])
+        loss = 0
+        for l in ls:
+            loss = loss + l
+        return loss
+
+
+def _patchgan_forward(model, plan, x, pad, sigmoid):
+    """A PatchGAN Sequential on HIP kernels: implicit-GEMM 4x4 conv (+bias, +LeakyReLU(0.2) in the
+    epilogue for layer 0), InstanceNorm + LeakyReLU fused, and the optional fp32 sigmoid."""
+    h = x
+    for idx, stride, use_in in plan:
+        c = model[idx]
+        if use_in is None:      # last conv: raw logits
+            h = HF.conv2d(h, c.weight, c.bias, stride=stride, pad=pad)
+        elif use_in:
+            h = HF.instance_norm(HF.conv2d(h, c.weight, c.bias, stride=stride, pad=pad), act="lrelu")
+        else:
+            h = HF.conv2d(h, c.weight, c.bias, stride=stride, pad=pad, act="lrelu")
+    return HF.sigmoid(h) if sigmoid else h
 
 
 class NLayerDiscriminator(nn.Module):
     """PatchGAN D, DSGAN/models/networks.py:533-579.  Same ``model.<i>`` Sequential indices as
-    the reference (conv holders at 0, 2, 5, 8, 11), forward on HIP kernels: implicit-GEMM 4x4
-    conv (+bias, +LeakyReLU(0.2) in the epilogue for layer 0) and InstanceNorm + LeakyReLU fused."""
+    the reference (conv holders at 0, 2, 5, 8, 11; ``use_sigmoid`` appends nn.Sigmoid as model.12),
+    forward on HIP kernels (_patchgan_forward)."""
 
     def __init__(self, input_nc, ndf=64, n_layers=3, norm_layer=nn.BatchNorm2d, use_sigmoid=False):
         super().__init__()
@@ -139,8 +203,6 @@ class NLayerDiscriminator(nn.Module):
             use_bias = norm_layer.func == nn.InstanceNorm2d
         else:
             use_bias = norm_layer == nn.InstanceNorm2d
-        if use_sigmoid:
-            raise NotImplementedError("use_sigmoid=True is only reachable with --no_lsgan (LSGAN)")
         kw, padw = 4, 1
         seq = [nn.Conv2d(input_nc, ndf, kernel_size=kw, stride=2, padding=padw), nn.LeakyReLU(0.2, True)]
         self.plan = [(0, 2, False)]  # (index, stride, instance_norm)
@@ -156,16 +218,103 @@ class NLayerDiscriminator(nn.Module):
                 norm_layer(ndf * nf_mult), nn.LeakyReLU(0.2, True)]
         self.plan.append((len(seq), 1, None))
         seq += [nn.Conv2d(ndf * nf_mult, 1, kernel_size=kw, stride=1, padding=padw)]
+        self.use_sigmoid = bool(use_sigmoid)
+        if use_sigmoid:
+            seq += [nn.Sigmoid()]
         self.model = nn.Sequential(*seq)
 
     def forward(self, x):
-        h = x
-        for idx, stride, use_in in self.plan:
-            c = self.model[idx]
-            if use_in is None:      # last conv: raw logits
-                h = HF.conv2d(h, c.weight, c.bias, stride=stride, pad=1)
-            elif use_in:
-                h = HF.instance_norm(HF.conv2d(h, c.weight, c.bias, stride=stride, pad=1), act="lrelu")
-            else:
-                h = HF.conv2d(h, c.weight, c.bias, stride=stride, pad=1, act="lrelu")
-        return h
+        return _patchgan_forward(self.model, self.plan, x, 1, self.use_sigmoid)
+
+
+class NLayerDiscriminator_multi(nn.Module):
+    """One scale of the multi-scale D, DSGAN/models/networks.py:582-631 (getIntermFeat=False): the
+    PatchGAN with ``padw = ceil(1.5) = 2``, a bias on every conv and channels doubling up to 512."""
+
+    def __init__(self, input_nc, ndf=64, n_layers=3, norm_layer=nn.BatchNorm2d, use_sigmoid=False, getIntermFeat=False):
+        super().__init__()
+        if getIntermFeat:
+            raise NotImplementedError("NLayerDiscriminator_multi: getIntermFeat=True is not on the DS-GAN path")
+        self.n_layers = n_layers
+        kw = 4
+        self.padw = padw = int(math.ceil((kw - 1.0) / 2))
+        seq = [nn.Conv2d(input_nc, ndf, kernel_size=kw, stride=2, padding=padw), nn.LeakyReLU(0.2, True)]
+        self.plan = [(0, 2, False)]
+        nf = ndf
+        for n in range(1, n_layers):
+            nf_prev, nf = nf, min(nf * 2, 512)
+            self.plan.append((len(seq), 2, True))
+            seq += [nn.Conv2d(nf_prev, nf, kernel_size=kw, stride=2, padding=padw), norm_layer(nf),
+                    nn.LeakyReLU(0.2, True)]
+        nf_prev, nf = nf, min(nf * 2, 512)
+        self.plan.append((len(seq), 1, True))
+        seq += [nn.Conv2d(nf_prev, nf, kernel_size=kw, stride=1, padding=padw), norm_layer(nf), nn.LeakyReLU(0.2, True)]
+        self.plan.append((len(seq), 1, None))
+        seq += [nn.Conv2d(nf, 1, kernel_size=kw, stride=1, padding=padw)]
+        self.use_sigmoid = bool(use_sigmoid)
+        if use_sigmoid:
+            seq += [nn.Sigmoid()]
+        self.model = nn.Sequential(*seq)
+
+    def forward(self, x):
+        return _patchgan_forward(self.model, self.plan, x, self.padw, self.use_sigmoid)
+
+
+class PixelDiscriminator(nn.Module):
+    """DSGAN/models/networks.py:634-656: three 1x1 convs (``net.{0,2,5}``) on the pointwise kernels."""
+
+    def __init__(self, input_nc, ndf=64, norm_layer=nn.BatchNorm2d, use_sigmoid=False):
+        super().__init__()
+        if type(norm_layer) == functools.partial:
+            use_bias = norm_layer.func == nn.InstanceNorm2d
+        else:
+            use_bias = norm_layer == nn.InstanceNorm2d
+        net = [nn.Conv2d(input_nc, ndf, kernel_size=1, stride=1, padding=0), nn.LeakyReLU(0.2, True),
+               nn.Conv2d(ndf, ndf * 2, kernel_size=1, stride=1, padding=0, bias=use_bias), norm_layer(ndf * 2),
+               nn.LeakyReLU(0.2, True),
+               nn.Conv2d(ndf * 2, 1, kernel_size=1, stride=1, padding=0, bias=use_bias)]
+        self.use_sigmoid = bool(use_sigmoid)
+        if use_sigmoid:
+            net.append(nn.Sigmoid())
+        self.net = nn.Sequential(*net)
+
+    def forward(self, x):
+        c0, c2, c5 = self.net[0], self.net[2], self.net[5]
+        h = HF.conv2d(x, c0.weight, c0.bias, act="lrelu")
+        h = HF.instance_norm(HF.conv2d(h, c2.weight, c2.bias), act="lrelu")
+        h = HF.conv2d(h, c5.weight, c5.bias)
+        return HF.sigmoid(h) if self.use_sigmoid else h
+
+
+class MultiscaleDiscriminator(nn.Module):
+    """DSGAN/models/networks.py:659-699 with num_D scales and getIntermFeat=False: ``layer<i>`` are
+    the scales' Sequentials (keys ``layer{0,1,2}.{0,2,5,8,11}.{weight,bias}``); ``result[i]`` is
+    ``[layer<num_D-1-i>(input pooled i times)]``, the pool AvgPool2d(3, 2, 1, count_include_pad=False)
+    in one HIP pass per level.  An input that needs a gradient feeds a scale's stem conv and the next
+    pool: the two data-grads meet in one buffer (HF.share)."""
+
+    def __init__(self, input_nc, ndf=64, n_layers=3, norm_layer=nn.BatchNorm2d, use_sigmoid=False, num_D=3,
+                 getIntermFeat=False):
+        super().__init__()
+        if getIntermFeat:
+            raise NotImplementedError("MultiscaleDiscriminator: getIntermFeat=True is not on the DS-GAN path")
+        self.num_D, self.n_layers, self.getIntermFeat = num_D, n_layers, False
+        self.use_sigmoid = bool(use_sigmoid)
+        for i in range(num_D):
+            netD = NLayerDiscriminator_multi(input_nc, ndf, n_layers, norm_layer, use_sigmoid, False)
+            setattr(self, "layer" + str(i), netD.model)
+            self.plan, self.padw = netD.plan, netD.padw
+        self.downsample = nn.AvgPool2d(3, stride=2, padding=[1, 1], count_include_pad=False)
+
+    def forward(self, input):
+        result = []
+        x = input
+        for i in range(self.num_D):
+            last = i == self.num_D - 1
+            if not last and torch.is_grad_enabled() and x.requires_grad:
+                x = HF.share(x)
+            model = getattr(self, "layer" + str(self.num_D - 1 - i))
+            result.append([_patchgan_forward(model, self.plan, x, self.padw, self.use_sigmoid)])
+            if not last:
+                x = HF.avg_pool3s2(x)
+        return result

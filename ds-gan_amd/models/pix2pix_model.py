@@ -63,11 +63,7 @@ class _CaptureDeclined(RuntimeError):
     """Graph A's capture failed on some rank; every rank raises this together (one agreement)."""
 
 
-def _fusable(*xs):
-    """Loss terms HF.loss_sum takes: 0-d fp32 device tensors (a disabled term may be a python 0)."""
-    ts = [x for x in xs if not (not torch.is_tensor(x) and x == 0)]
-    return bool(ts) and len(ts) <= 8 and all(torch.is_tensor(x) and x.dim() == 0 and x.dtype == torch.float32
-                                             and x.is_cuda for x in ts)
+from .networks import _fusable   # noqa: E402 -- the loss terms HF.loss_sum takes
 from .vgg import Vgg16
 
 POOL_SEED = 20   # DSGAN/train.py:48 setup_seed(20): the ImagePool's RNG on ranks > 0 is offset from it
@@ -111,7 +107,10 @@ class Pix2PixModel(BaseModel):
             W, r = hdist.world_size(), hdist.rank()
             # one process: the global python `random`, consumed exactly as the reference does
             self.fake_AB_pool = ImagePool(opt.pool_size, rng=None if W == 1 else random.Random(POOL_SEED + 1000 * r))
-            self.criterionGAN = networks.GANLoss(use_lsgan=opt.no_lsgan).to(self.device)
+            if opt.which_model_netD == "multi":   # DSGAN/models/pix2pix_model.py:111-114
+                self.criterionGAN = networks.GANLoss_multi(use_lsgan=opt.no_lsgan).to(self.device)
+            else:
+                self.criterionGAN = networks.GANLoss(use_lsgan=opt.no_lsgan).to(self.device)
             self.criterionL1 = HF.l1_loss
             self.vgg = Vgg16(getattr(opt, "vgg_weights", "") or None).to(self.device)
             # flat param/grad buffers + fused Adam (one launch per network per step)
@@ -202,7 +201,11 @@ class Pix2PixModel(BaseModel):
             else:
                 HF.copy_into(AB[N:], self.real_B)
             pred = self.netD(AB)
-            pred_fake, pred_real = pred[:N], pred[N:]
+            if isinstance(pred, list):   # the multi-scale D: every scale's tensor splits the same way
+                pred_fake = [[t[:N] for t in s] for s in pred]
+                pred_real = [[t[N:] for t in s] for s in pred]
+            else:
+                pred_fake, pred_real = pred[:N], pred[N:]
         else:
             pred_fake = self.netD(fake_AB)
             real_AB = HF.cat_channels(self.real_A, self.real_B) if self.use_condition == 1 else self.real_B

@@ -556,6 +556,29 @@ int dsgan_ssim_fwd(const float* real, const float* fake, float a, float b, int p
 int dsgan_ssim_bwd(const float* real, const float* fake, float a, float b, int planes, int H,
                    int W, const float* win11, const float* coef, const float* gout, float gcoef,
                    float* dfake, int accumulate, hipStream_t stream);
+/* ---- LSGAN objective and the multi-scale D's input pyramid (lsgan.hip); fp32 in every mode ----
+ * sigmoid: nn.Sigmoid, the last layer of a use_sigmoid discriminator (networks.py:571-572), with the
+ * accurate expf (finite for any finite x); the backward takes the saved OUTPUT: dx (+)= dy*y*(1-y).
+ * mse_const: nn.MSELoss against a constant label (GANLoss / GANLoss_multi, networks.py:148-149,
+ * :175-176): out[0] = mean((x - target)^2) through dsgan_loss_parts() block partials summed in a
+ * fixed order; dx (+)= gout[0] * 2 (x - target) / n. */
+int dsgan_sigmoid_fwd(const float* x, long n, float* y, hipStream_t stream);
+int dsgan_sigmoid_bwd(const float* y, const float* dy, long n, float* dx, int accumulate, hipStream_t stream);
+int dsgan_mse_const_fwd(const float* x, long n, float target, float* out, float* part, hipStream_t stream);
+int dsgan_mse_const_bwd(const float* x, long n, float target, const float* gout, float* dx, int accumulate,
+                        hipStream_t stream);
+/* AvgPool2d(3, stride=2, padding=1, count_include_pad=False) on NCHW fp32 with batch strides
+ * (MultiscaleDiscriminator.downsample, networks.py:675): y is [N][C][(H-1)/2+1][(W-1)/2+1], each
+ * output the mean of its window's taps inside the image.  form 0 takes the 16-byte form where it
+ * applies (_fast_supported: W % 8 == 0, batch strides % 4 == 0, 16-byte aligned pointers), 1 forces
+ * the scalar form, 2 the 16-byte form (an error where it does not apply); both give the same bits.
+ * _bwd (H, W = the INPUT's size) gathers: dx (+)= sum of dy / taps over the <= 4 windows that hold
+ * the pixel, in a fixed order (its 16-byte form needs W % 4 == 0 and an aligned dx). */
+int dsgan_avgpool3s2_fast_supported(const float* x, long x_bs, const float* y, long y_bs, int C, int H, int W);
+int dsgan_avgpool3s2_fwd(const float* x, long x_bs, float* y, long y_bs, int N, int C, int H, int W, int form,
+                         hipStream_t stream);
+int dsgan_avgpool3s2_bwd(const float* dy, long dy_bs, float* dx, long dx_bs, int N, int C, int H, int W,
+                         int accumulate, int form, hipStream_t stream);
 /* input pipeline, DSGAN/data/aligned_dataset.py:38-86 (ToTensor, crop, Normalize(0.5,0.5), flip,
  * optional gray): src uint8 [N][H][W][3] (already cropped), flip int [N] (device), dst fp32
  * [N][3 or 1][H][W]; bit-exact with the reference's torch CPU transforms. */
