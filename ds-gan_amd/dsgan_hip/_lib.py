@@ -176,6 +176,12 @@ SIGNATURES = {
     "dsgan_avgpool3s2_fast_supported": [P, L, P, L, I, I, I],
     "dsgan_avgpool3s2_fwd": [P, L, P, L, I, I, I, I, I, S],
     "dsgan_avgpool3s2_bwd": [P, L, P, L, I, I, I, I, I, I, S],
+    # batchnorm.hip
+    "dsgan_batchnorm_workspace": [I, I, I],
+    "dsgan_batchnorm_plan": [I, I, I],
+    "dsgan_batchnorm_tune": [I, I],
+    "dsgan_batchnorm_fwd": [P, L, P, P, P, L, P, P, P, P, P, I, I, I, I, F, F, F, I, P, L, S],
+    "dsgan_batchnorm_bwd": [P, L, P, L, P, P, P, P, P, L, P, P, I, I, I, I, F, I, P, L, S],
     # vggconv.hip
     "dsgan_vconv_supported": [I, I, I, I],
     "dsgan_vconv_tune": [I, I],
@@ -210,7 +216,7 @@ def load():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = (ctypes.c_char_p if name == "dsgan_last_error_string"
-                      else ctypes.c_long if name.endswith(("_workspace", "_parts", "_size", "_need")) else ctypes.c_int)
+                      else ctypes.c_long if name.endswith(("_workspace", "_parts", "_size", "_need", "_plan")) else ctypes.c_int)
     _lib = lib
     return lib
 

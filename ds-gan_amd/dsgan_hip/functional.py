@@ -1622,6 +1622,86 @@ def instance_norm(x, act=None, res=None):
     return InstanceNormFn.apply(x, res, act)
 
 
+# ------------------------------------------------------------------------------------------
+# BatchNorm2d (affine, running statistics) + act: the PatchGAN under --norm batch (batchnorm.hip)
+# ------------------------------------------------------------------------------------------
+
+def _bn_check(shape, training, momentum):
+    if momentum is None:
+        raise NotImplementedError("batch_norm: momentum=None (a cumulative moving average) is not on the HIP path")
+    if training and shape[0] * shape[2] * shape[3] == 1:   # torch's own error (F.batch_norm), before any launch
+        raise ValueError("Expected more than 1 value per channel when training, got input size %s"
+                         % (torch.Size(shape),))
+
+
+def batchnorm_raw(x, weight, bias, running_mean, running_var, num_batches_tracked, training, momentum=0.1, eps=IN_EPS,
+                  act=None, out=None):
+    """y = act(BN(x)) with the batch's statistics (training: the running buffers and the int64 counter
+    are updated on the device) or the running buffers (eval).  Returns (y, mean, rstd): what the
+    output was normalised with, for batchnorm_bwd_raw."""
+    x, xbs = nchw(x)
+    N, C, H, W = x.shape
+    _bn_check(x.shape, training, momentum)
+    y = out if out is not None else _empty(N, C, H, W, x)
+    y4, ybs = nchw(y)
+    mean = torch.empty(C, device=x.device, dtype=torch.float32)
+    rstd = torch.empty(C, device=x.device, dtype=torch.float32)
+    with _timed(AUX_TIMER, 0.0, ("bn_fwd", N, C, H, W, act, bool(training)), "batchnorm", 2 * _nb(x)):
+        call("dsgan_batchnorm_fwd", ptr(x), xbs, ptr(weight), ptr(bias), ptr(y4), ybs, ptr(mean), ptr(rstd),
+             ptr(running_mean), ptr(running_var), ptr(num_batches_tracked), N, C, H * W, ACT[act], LRELU_SLOPE,
+             float(eps), float(momentum), 1 if training else 0,
+             *wsa(_ws("dsgan_batchnorm_workspace", N, C, H * W, like=x)), stream())
+    return y4, mean, rstd
+
+
+def batchnorm_bwd_raw(dy, x, weight, bias, mean, rstd, act, training, dweight=None, dbias=None):
+    """dx of batchnorm_raw; dweight / dbias (a pair, or neither) are accumulated into."""
+    dy, dybs = nchw(dy)
+    x, xbs = nchw(x)
+    N, C, H, W = x.shape
+    dx = _empty(N, C, H, W, x)
+    with _timed(AUX_TIMER, 0.0, ("bn_bwd", N, C, H, W, act, bool(training)), "batchnorm", 3 * _nb(x)):
+        call("dsgan_batchnorm_bwd", ptr(dy), dybs, ptr(x), xbs, ptr(weight), ptr(bias), ptr(mean), ptr(rstd), ptr(dx),
+             C * H * W, ptr(dweight), ptr(dbias), N, C, H * W, ACT[act], LRELU_SLOPE, 1 if training else 0,
+             *wsa(_ws("dsgan_batchnorm_workspace", N, C, H * W, like=x)), stream())
+    return dx
+
+
+class BatchNormFn(torch.autograd.Function):
+    """y = act(BatchNorm2d(x)) -- only x is saved; the backward recomputes z from x, mean, rstd."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, bn, act):
+        y, mean, rstd = batchnorm_raw(x, weight, bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
+                                      bn.training, bn.momentum, bn.eps, act)
+        ctx.act, ctx.training = act, bool(bn.training)
+        ctx.save_for_backward(x, weight, bias, mean, rstd)
+        ctx.w_ref, ctx.b_ref = weight, bias
+        ctx.box = _box(x)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight, bias, mean, rstd = ctx.saved_tensors
+        gw = _grad_buf(ctx.w_ref) if ctx.needs_input_grad[1] else None
+        gb = _grad_buf(ctx.b_ref) if ctx.needs_input_grad[2] else None
+        if (gw is None) != (gb is None):
+            raise RuntimeError("batch_norm: weight and bias must both need a gradient, or neither")
+        dx = batchnorm_bwd_raw(dy, x, weight, bias, mean, rstd, ctx.act, ctx.training, gw, gb)
+        _params_done(ctx.w_ref, ctx.b_ref)
+        return _give(ctx.box, dx), None, None, None, None
+
+
+def batch_norm(x, bn, act=None):
+    """``act(bn(x))`` for an ``nn.BatchNorm2d`` (affine, with running statistics): its weight, bias,
+    buffers, eps, momentum and ``training`` are read from the module."""
+    if bn.weight is None or bn.running_mean is None:
+        raise NotImplementedError("batch_norm: needs affine=True and track_running_stats=True (the reference's "
+                                  "get_norm_layer('batch'))")
+    _bn_check(x.shape, bn.training, bn.momentum)
+    return BatchNormFn.apply(x, bn.weight, bn.bias, bn, act)
+
+
 def _instnorm_cat(x, skip, act, slot):
     """(cat(act(IN(x)), skip), mean, rstd): the IN kernel writes into the first channels of the
     concatenation; the skip is copied behind them unless it already sits there (``slot``'s tail)."""

@@ -107,9 +107,11 @@ class BaseModel:
                 print("loading the model from %s" % path)
                 state_dict = torch.load(path, map_location="cpu", weights_only=True)
                 state_dict = OrderedDict((k[7:] if k.startswith("module.") else k, v) for k, v in state_dict.items())
-                state_dict = {k: v for k, v in state_dict.items()
-                              if not (k.endswith("running_mean") or k.endswith("running_var"))}
                 own = net.state_dict()
+                # the reference's pre-0.4 InstanceNorm patch (:108-109): running statistics saved for a
+                # layer that tracks none are dropped; a BatchNorm's own buffers load like any key
+                state_dict = {k: v for k, v in state_dict.items()
+                              if k in own or not (k.endswith("running_mean") or k.endswith("running_var"))}
                 bad = ["%s: checkpoint %s vs model %s" % (k, tuple(v.shape), tuple(own[k].shape))
                        for k, v in state_dict.items() if k in own and own[k].shape != v.shape]
                 if bad:

@@ -8,7 +8,8 @@ without the trailing ``nn.Sigmoid`` (``use_sigmoid``).  Both objectives are here
 (the default) and least squares (``GANLoss(use_lsgan=True)`` / ``GANLoss_multi``), which the
 reference's backwards-wired ``--no_lsgan`` turns ON together with the sigmoid (quirk q3).  ``multi``
 without the sigmoid raises: the reference pairs it with ``BCELoss`` on raw logits, which fails in
-torch itself.  Other reference generators are out of scope and raise the
+torch itself.  ``--norm batch`` builds the ``basic`` / ``n_layers`` PatchGAN on BatchNorm2d (fused
+BatchNorm + LeakyReLU kernels, HF.batch_norm).  Other reference generators are out of scope and raise the
 reference's own error.
 """
 import functools
@@ -102,12 +103,17 @@ def define_G(input_nc, output_nc, ngf, which_model_netG, norm="batch", use_dropo
 def define_D(input_nc, ndf, which_model_netD, n_layers_D=3, norm="batch", use_sigmoid=False,
              init_type="normal", gpu_ids=()):
     """DSGAN/models/networks.py:115-131.  The discriminators run InstanceNorm (affine=False, the
-    reference default ``--norm instance``) fused into their conv kernels; ``--norm batch`` (affine
-    BatchNorm2d with running stats) and ``none`` are not on the DS-GAN path and raise instead of
+    reference default ``--norm instance``) fused into their conv kernels.  ``--norm batch`` (affine
+    BatchNorm2d with running statistics, bias-free convs in front of it) is built for the ``basic`` /
+    ``n_layers`` PatchGAN on the fused BatchNorm kernels (HF.batch_norm); ``pixel`` / ``multi`` with it,
+    and ``none`` (which fails in the reference itself: ``norm_layer`` is None), raise instead of
     silently training a different discriminator."""
-    if norm != "instance":
+    if norm == "batch" and which_model_netD in ("pixel", "multi"):
+        raise NotImplementedError("define_D: norm [batch] is not supported for the [%s] discriminator on the "
+                                  "MI355X build (basic / n_layers only)" % which_model_netD)
+    if norm not in ("instance", "batch"):
         raise NotImplementedError("define_D: norm [%s] is not supported by the MI355X PatchGAN "
-                                  "(instance only, the reference default)" % norm)
+                                  "(instance, the reference default, or batch)" % norm)
     norm_layer = get_norm_layer(norm_type=norm)
     if which_model_netD == "basic":
         netD = NLayerDiscriminator(input_nc, ndf, n_layers=3, norm_layer=norm_layer, use_sigmoid=use_sigmoid)
@@ -179,12 +185,15 @@ class GANLoss_multi(nn.Module):
 
 def _patchgan_forward(model, plan, x, pad, sigmoid):
     """A PatchGAN Sequential on HIP kernels: implicit-GEMM 4x4 conv (+bias, +LeakyReLU(0.2) in the
-    epilogue for layer 0), InstanceNorm + LeakyReLU fused, and the optional fp32 sigmoid."""
+    epilogue for layer 0), InstanceNorm + LeakyReLU fused (or, where the layer after the conv is a
+    BatchNorm2d, the bias-free conv and BatchNorm + LeakyReLU fused), and the optional fp32 sigmoid."""
     h = x
     for idx, stride, use_in in plan:
         c = model[idx]
         if use_in is None:      # last conv: raw logits
             h = HF.conv2d(h, c.weight, c.bias, stride=stride, pad=pad)
+        elif use_in and isinstance(model[idx + 1], nn.BatchNorm2d):
+            h = HF.batch_norm(HF.conv2d(h, c.weight, None, stride=stride, pad=pad), model[idx + 1], act="lrelu")
         elif use_in:
             h = HF.instance_norm(HF.conv2d(h, c.weight, c.bias, stride=stride, pad=pad), act="lrelu")
         else:
@@ -192,10 +201,17 @@ def _patchgan_forward(model, plan, x, pad, sigmoid):
     return HF.sigmoid(h) if sigmoid else h
 
 
+def has_batch_stats(net):
+    """True when ``net`` normalises with statistics taken across the batch (a BatchNorm layer): its
+    outputs for one sample then depend on the other samples of the pass."""
+    return any(isinstance(m, nn.modules.batchnorm._BatchNorm) for m in net.modules())
+
+
 class NLayerDiscriminator(nn.Module):
     """PatchGAN D, DSGAN/models/networks.py:533-579.  Same ``model.<i>`` Sequential indices as
     the reference (conv holders at 0, 2, 5, 8, 11; ``use_sigmoid`` appends nn.Sigmoid as model.12),
-    forward on HIP kernels (_patchgan_forward)."""
+    forward on HIP kernels (_patchgan_forward).  ``norm`` records which normalisation the plan's
+    normalised layers use ("instance" or "batch")."""
 
     def __init__(self, input_nc, ndf=64, n_layers=3, norm_layer=nn.BatchNorm2d, use_sigmoid=False):
         super().__init__()
@@ -203,9 +219,10 @@ class NLayerDiscriminator(nn.Module):
             use_bias = norm_layer.func == nn.InstanceNorm2d
         else:
             use_bias = norm_layer == nn.InstanceNorm2d
+        self.norm = "instance" if use_bias else "batch"
         kw, padw = 4, 1
         seq = [nn.Conv2d(input_nc, ndf, kernel_size=kw, stride=2, padding=padw), nn.LeakyReLU(0.2, True)]
-        self.plan = [(0, 2, False)]  # (index, stride, instance_norm)
+        self.plan = [(0, 2, False)]  # (index, stride, normalised)
         nf_mult = 1
         for n in range(1, n_layers):
             nf_prev, nf_mult = nf_mult, min(2 ** n, 8)

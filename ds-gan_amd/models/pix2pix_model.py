@@ -24,7 +24,18 @@ Deliberate, documented deviations:
     an overflowed step is skipped; the logged losses are the unscaled ones;
   * --nonfinite_guard (on by default in bf16): the same device-side check with a unit scale -- an
     optimizer step whose flat gradient holds inf/nan is skipped (the reference would write NaN
-    into its weights and never recover); with finite gradients nothing changes.
+    into its weights and never recover); with finite gradients nothing changes;
+  * --norm batch (the basic / n_layers D on BatchNorm2d): under ``torchrun`` each rank normalises
+    with the statistics of its own chunk and keeps its own running buffers -- what the reference's
+    nn.DataParallel replicas do; the statistics are not synchronised across ranks, so a multi-rank
+    run is not bit-equal to one process on the global batch.  The gradients of the BatchNorm weight /
+    bias go through the flat-gradient all-reduce like every other parameter.  One
+    ``optimize_parameters`` updates each BatchNorm's running buffers three times (fake pass, real
+    pass, the G step's pass; ``num_batches_tracked`` grows by 3), on the device, so graph replays
+    advance them too.  backward_D always runs the two D passes, fake first, whatever ``d_batch`` /
+    DSGAN_D_BATCH say: the stacked batch-2N pass would mix the two batches' statistics.  A step
+    that the fp16 loss scaler or the non-finite guard skips has still updated the running buffers
+    (the forward ran), as under torch's GradScaler.
 """
 import os
 import random
@@ -158,6 +169,9 @@ class Pix2PixModel(BaseModel):
             self.step_calls = {"G": 0, "D": 0}
             # backward_D's stacked batch-2N D pass (D_BATCH); an attribute so tests can compare the two forms
             self.d_batch = D_BATCH
+            # a D with batch statistics (--norm batch) never takes the stacked pass: it would mix the
+            # fake and the real batch's statistics (the two passes run fake first, as the reference's)
+            self.d_batch_stats = networks.has_batch_stats(self.netD)
             self.vgg_overlap = VGG_OVERLAP
             self._pre_perc = None
 
@@ -188,7 +202,7 @@ class Pix2PixModel(BaseModel):
         else:
             fake_AB = self.fake_B
         fake_AB = fake_AB.detach()
-        if self.d_batch and fake_AB.dim() == 4 and fake_AB.dtype == torch.float32:
+        if self.d_batch and not self.d_batch_stats and fake_AB.dim() == 4 and fake_AB.dtype == torch.float32:
             # the fake and real passes as ONE batch-2N pass of D (D's ops are per-sample: the same
             # outputs, half the launches); neither half needs an input grad
             N, C, H, W = fake_AB.shape

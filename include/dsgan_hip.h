@@ -579,6 +579,38 @@ int dsgan_avgpool3s2_fwd(const float* x, long x_bs, float* y, long y_bs, int N, 
                          hipStream_t stream);
 int dsgan_avgpool3s2_bwd(const float* dy, long dy_bs, float* dx, long dx_bs, int N, int C, int H, int W,
                          int accumulate, int form, hipStream_t stream);
+/* ---- BatchNorm2d + activation (batchnorm.hip): the PatchGAN under --norm batch; fp32 in every mode ----
+ * nn.BatchNorm2d(C, affine=True, track_running_stats=True) (networks.py:21-30) on NCHW fp32 with
+ * batch strides and dense planes of any size and alignment, fused with the activation that follows:
+ * y = act(gamma_c * (x - mean_c) * rstd_c + beta_c).
+ * training != 0: mean_c / the biased variance are taken over the N*HW values of channel c (never as
+ *   E[x^2] - E[x]^2); running_mean <- (1 - momentum) running_mean + momentum mean, running_var likewise
+ *   with the unbiased variance, *num_batches_tracked += 1 (int64, nullable), all on the device.
+ *   N*HW == 1 is refused (torch's "Expected more than 1 value per channel when training").
+ * training == 0: the running buffers are read and left alone.
+ * mean / rstd ([C]) receive what the output was normalised with (in eval mode the running mean and
+ * 1/sqrt(running_var + eps)) for the backward, which recomputes z from x:
+ *   dz = dy * act'(z), dbeta = sum dz, dgamma = sum dz * xhat,
+ *   dx = gamma rstd (dz - dbeta/m - xhat dgamma/m)   (training == 0: gamma rstd dz);
+ * dgamma / dbeta are nullable as a pair (frozen parameters) and are ACCUMULATED into.
+ * Both calls take dsgan_batchnorm_workspace(N, C, HW) fp32 elements of scratch (0 for form 0).
+ * dsgan_batchnorm_plan: the launch form both calls use for the shape --
+ *   0  one 1024-thread workgroup per channel, the channel held in registers (N*HW <= 16384);
+ *   1  split: per-(slice, channel) partials to scratch, then an apply launch that combines a channel's
+ *      partials (at most 64) in slice order.
+ * dsgan_batchnorm_tune(0, v): planner knob (measurement tools): 0 the planner's choice, 1 form 0
+ * wherever it fits, 2 form 1 everywhere; v < 0 reads; returns the previous value. */
+long dsgan_batchnorm_workspace(int N, int C, int HW);
+long dsgan_batchnorm_plan(int N, int C, int HW);
+int dsgan_batchnorm_tune(int key, int val);
+int dsgan_batchnorm_fwd(const float* x, long x_bs, const float* gamma, const float* beta, float* y, long y_bs,
+                        float* mean, float* rstd, float* running_mean, float* running_var, long* num_batches_tracked,
+                        int N, int C, int HW, int act, float slope, float eps, float momentum, int training,
+                        float* ws, long ws_elems, hipStream_t stream);
+int dsgan_batchnorm_bwd(const float* dy, long dy_bs, const float* x, long x_bs, const float* gamma, const float* beta,
+                        const float* mean, const float* rstd, float* dx, long dx_bs, float* dgamma, float* dbeta,
+                        int N, int C, int HW, int act, float slope, int training,
+                        float* ws, long ws_elems, hipStream_t stream);
 /* input pipeline, DSGAN/data/aligned_dataset.py:38-86 (ToTensor, crop, Normalize(0.5,0.5), flip,
  * optional gray): src uint8 [N][H][W][3] (already cropped), flip int [N] (device), dst fp32
  * [N][3 or 1][H][W]; bit-exact with the reference's torch CPU transforms. */
