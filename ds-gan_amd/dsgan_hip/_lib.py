@@ -182,6 +182,14 @@ SIGNATURES = {
     "dsgan_batchnorm_tune": [I, I],
     "dsgan_batchnorm_fwd": [P, L, P, P, P, L, P, P, P, P, P, I, I, I, I, F, F, F, I, P, L, S],
     "dsgan_batchnorm_bwd": [P, L, P, L, P, P, P, P, P, L, P, P, I, I, I, I, F, I, P, L, S],
+    # unet.hip
+    "dsgan_prelu_workspace": [I, L],
+    "dsgan_prelu_fwd": [P, L, L, P, L, L, P, P, L, I, S],
+    "dsgan_prelu_bwd": [P, L, P, L, L, P, L, L, P, P, L, P, L, P, I, P, L, S],
+    "dsgan_dropout_fwd": [P, L, P, L, I, L, L, L, P, P, L, F, S],
+    "dsgan_dropout_apply": [P, L, P, L, I, L, L, L, P, L, L, F, S],
+    "dsgan_tanh_fwd": [P, L, P, S],
+    "dsgan_tanh_bwd": [P, P, L, P, I, S],
     # vggconv.hip
     "dsgan_vconv_supported": [I, I, I, I],
     "dsgan_vconv_tune": [I, I],

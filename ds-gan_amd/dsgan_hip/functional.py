@@ -2656,3 +2656,195 @@ class AvgPool3s2Fn(torch.autograd.Function):
 def avg_pool3s2(x):
     """AvgPool2d(3, stride=2, padding=1, count_include_pad=False) (MultiscaleDiscriminator.downsample)."""
     return AvgPool3s2Fn.apply(x)
+
+
+# ------------------------------------------------------------------------------------------
+# U-Net generator glue (unet.hip; DSGAN/models/networks.py:445-529): ConvTranspose2d 4x4/s2/p1,
+# nn.PReLU() over a channel concatenation, nn.Dropout from a counter-based generator, nn.Tanh
+# ------------------------------------------------------------------------------------------
+
+# ConvTranspose2d(k4, s2, p1) doubles the plane exactly as (k3, s2, p1, op1) does, and ConvT3s2Fn reads
+# the kernel size off the weight: forward conv_dgrad_raw(.., 2, 1, bias), backward conv_fwd_raw(dy, w,
+# None, 2, 1), conv_wgrad_raw(x, dy, gw, 2, 1), channel_sum_raw.
+ConvT4s2Fn = ConvT3s2Fn
+
+
+def conv_transpose4s2(x, w, b=None):
+    """nn.ConvTranspose2d(Cin, Cout, kernel_size=4, stride=2, padding=1): w is [Cin, Cout, 4, 4]."""
+    if w.dim() != 4 or tuple(w.shape[2:]) != (4, 4) or w.shape[0] != x.shape[1]:
+        raise ValueError("conv_transpose4s2: weight %s does not fit input %s" % (tuple(w.shape), tuple(x.shape)))
+    return ConvT4s2Fn.apply(x, w, b)
+
+
+def _dense4(t, what):
+    """(t, batch stride) of a per-sample dense NCHW tensor a kernel writes into."""
+    t4, bs = nchw(t)
+    if t4.data_ptr() != t.data_ptr():
+        raise ValueError("%s: destination must be per-sample dense" % what)
+    return t4, bs
+
+
+class PReluCatFn(torch.autograd.Function):
+    """y = prelu(cat(a, b), weight) for an ``nn.PReLU()`` weight of one element (b None: prelu(a)).
+    The halves are read where they lie (own batch strides, e.g. a CatSlot's head and tail), the slope
+    from device memory.  The backward writes both input grads into one buffer (its channel slices are
+    da / db) and adds the slope's gradient into ``weight.grad`` through block partials summed in a
+    fixed order."""
+
+    @staticmethod
+    def forward(ctx, a, b, weight, out):
+        if weight.numel() != 1:
+            raise NotImplementedError("prelu: one slope (nn.PReLU(num_parameters=1)) only")
+        ctx.box_a, ctx.box_b = _box(a), (_box(b) if b is not None else None)
+        a, abs_ = nchw(a)
+        N, Ca, H, W = a.shape
+        Cb, bbs = 0, 0
+        if b is not None:
+            b, bbs = nchw(b)
+            if b.shape[0] != N or tuple(b.shape[2:]) != (H, W):
+                raise ValueError("prelu_cat: %s and %s do not concatenate" % (tuple(a.shape), tuple(b.shape)))
+            Cb = b.shape[1]
+        y = out if out is not None else _empty(N, Ca + Cb, H, W, a)
+        if tuple(y.shape) != (N, Ca + Cb, H, W):
+            raise ValueError("prelu_cat: out has shape %s" % (tuple(y.shape),))
+        y, ybs = _dense4(y, "prelu_cat")
+        with _timed(AUX_TIMER, 0.0, ("prelu_fwd", N, Ca, Cb, H, W), "prelu", 2 * _nb(y)):
+            call("dsgan_prelu_fwd", ptr(a), abs_, Ca * H * W, ptr(b), bbs, Cb * H * W, ptr(weight), ptr(y), ybs, N,
+                 stream())
+        ctx.save_for_backward(a, b, weight)
+        ctx.w_ref = weight
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        a, b, weight = ctx.saved_tensors
+        dy, dybs = nchw(dy)
+        N, Ca, H, W = a.shape
+        Cb = b.shape[1] if b is not None else 0
+        E = (Ca + Cb) * H * W
+        d = _empty(N, Ca + Cb, H, W, dy)
+        da, db = (d[:, :Ca], d[:, Ca:]) if b is not None else (d, None)
+        gw = _grad_buf(ctx.w_ref) if ctx.needs_input_grad[2] else None
+        with _timed(AUX_TIMER, 0.0, ("prelu_bwd", N, Ca, Cb, H, W), "prelu", 3 * _nb(d)):
+            call("dsgan_prelu_bwd", ptr(dy), dybs, ptr(a), nchw(a)[1], Ca * H * W, ptr(b),
+                 nchw(b)[1] if b is not None else 0, Cb * H * W, ptr(weight), ptr(da), E, ptr(db), E, ptr(gw), N,
+                 *wsa(_ws("dsgan_prelu_workspace", N, E, like=dy)), stream())
+        _params_done(ctx.w_ref)
+        return _give(ctx.box_a, da), (_give(ctx.box_b, db) if b is not None else None), None, None
+
+
+def prelu_cat(a, b, prelu_weight, out=None):
+    """``prelu(cat(a, b))`` with the learnable slope ``prelu_weight`` (pass the Parameter itself)."""
+    return PReluCatFn.apply(a, b, prelu_weight, out)
+
+
+def prelu(x, prelu_weight, out=None):
+    return PReluCatFn.apply(x, None, prelu_weight, out)
+
+
+class DropoutState:
+    """What fixes a dropout layer's masks: the 64-bit ``seed``, the ``stream`` id of the layer (the
+    rank is folded into it) and ``counter``, an int64 device tensor of one element that the forward
+    kernel advances -- a captured graph draws a fresh mask on every replay, nothing touches the host.
+    Call k of the layer drops element i iff word (i & 3) of Philox-4x32-10(key = seed, counter =
+    (i >> 2, k, stream)) is below round(p * 2^32)."""
+    __slots__ = ("seed", "stream", "counter")
+
+    def __init__(self, seed, stream, counter):
+        self.seed, self.stream, self.counter = int(seed) & (2 ** 63 - 1), int(stream), counter
+        if not 0 <= self.stream < 2 ** 32:
+            raise ValueError("DropoutState: stream id out of range")
+        if counter.dtype != torch.int64 or counter.numel() != 1:
+            raise ValueError("DropoutState: counter must be an int64 tensor of one element")
+
+
+def _dropout_thresh(p):
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError("dropout: p must be in [0, 1), got %r" % p)
+    return int(round(p * 2.0 ** 32))
+
+
+class DropoutFn(torch.autograd.Function):
+    """y = x * mask / (1 - p).  No mask tensor: the backward regenerates it from the call counter the
+    forward drew (a one-element device tensor)."""
+
+    @staticmethod
+    def forward(ctx, x, p, state, out):
+        ctx.box = _box(x)
+        x, xbs = nchw(x)
+        N, C, H, W = x.shape
+        y = out if out is not None else _empty(N, C, H, W, x)
+        y, ybs = _dense4(y, "dropout")
+        used = torch.empty(1, device=x.device, dtype=torch.int64)
+        ctx.args = (N, C * H * W, state.seed, state.stream, _dropout_thresh(p), 1.0 / (1.0 - float(p)))
+        N, E, seed, sid, thresh, scale = ctx.args
+        with _timed(AUX_TIMER, 0.0, ("dropout_fwd", N, C, H, W), "dropout", 2 * _nb(x)):
+            call("dsgan_dropout_fwd", ptr(x), xbs, ptr(y), ybs, N, E, seed, sid, ptr(state.counter), ptr(used), thresh,
+                 scale, stream())
+        ctx.save_for_backward(used)
+        ctx.shape = (N, C, H, W)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (used,) = ctx.saved_tensors
+        dy, dybs = nchw(dy)
+        N, E, seed, sid, thresh, scale = ctx.args
+        dx = _empty(*ctx.shape, dy)
+        with _timed(AUX_TIMER, 0.0, ("dropout_bwd",) + ctx.shape, "dropout", 2 * _nb(dx)):
+            call("dsgan_dropout_apply", ptr(dy), dybs, ptr(dx), E, N, E, seed, sid, ptr(used), 0, thresh, scale,
+                 stream())
+        return _give(ctx.box, dx), None, None, None
+
+
+def dropout(x, p, state, training, out=None):
+    """nn.Dropout(p) with the masks of ``state`` (a DropoutState).  Eval mode is the identity and
+    leaves the counter alone.  ``out``: a per-sample dense destination (e.g. a CatSlot's tail)."""
+    if not training or float(p) == 0.0:
+        if out is None:
+            return x
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise NotImplementedError("dropout: eval mode into `out` is a plain copy and records no gradient")
+        copy_into(out, x)
+        return out
+    return DropoutFn.apply(x, p, state, out)
+
+
+def dropout_mask(shape, seed, stream_id, counter, p=0.5, device="cuda"):
+    """The 0/1 mask (fp32, ``shape``) the dropout kernels use for call ``counter`` of the layer
+    (seed, stream_id): 1 where the element is kept."""
+    shape = tuple(int(s) for s in shape)
+    m = torch.empty(shape, device=device, dtype=torch.float32)
+    N = shape[0] if len(shape) > 1 else 1
+    E = m.numel() // N
+    call("dsgan_dropout_apply", None, 0, ptr(m), E, N, E, int(seed) & (2 ** 63 - 1), int(stream_id), None, int(counter),
+         _dropout_thresh(p), 1.0, stream())
+    return m
+
+
+class TanhFn(torch.autograd.Function):
+    """nn.Tanh in fp32; the backward reads the saved output, dx = dy * (1 - y^2), as torch's does."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.box = _box(x)
+        x = x.contiguous()
+        y = torch.empty_like(x)
+        with _timed(AUX_TIMER, 0.0, ("tanh_fwd", x.numel()), "tanh", _nb(x, y)):
+            call("dsgan_tanh_fwd", ptr(x), x.numel(), ptr(y), stream())
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (y,) = ctx.saved_tensors
+        dy = dy.contiguous()
+        dx = torch.empty_like(y)
+        with _timed(AUX_TIMER, 0.0, ("tanh_bwd", y.numel()), "tanh", _nb(y, dy, dx)):
+            call("dsgan_tanh_bwd", ptr(y), ptr(dy), y.numel(), ptr(dx), 0, stream())
+        return _give(ctx.box, dx)
+
+
+def tanh(x):
+    return TanhFn.apply(x)

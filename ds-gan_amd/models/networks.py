@@ -9,8 +9,10 @@ without the trailing ``nn.Sigmoid`` (``use_sigmoid``).  Both objectives are here
 reference's backwards-wired ``--no_lsgan`` turns ON together with the sigmoid (quirk q3).  ``multi``
 without the sigmoid raises: the reference pairs it with ``BCELoss`` on raw logits, which fails in
 torch itself.  ``--norm batch`` builds the ``basic`` / ``n_layers`` PatchGAN on BatchNorm2d (fused
-BatchNorm + LeakyReLU kernels, HF.batch_norm).  Other reference generators are out of scope and raise the
-reference's own error.
+BatchNorm + LeakyReLU kernels, HF.batch_norm).  ``define_G`` builds ``MixConvNeXtML`` and the
+``unet_128`` U-Net (models/unet.py: PReLU, dropout and tanh on HIP kernels, either norm); the other
+reference generators (``unet_256`` by name, the ResNets, ``gll``, ``cascaded``) are out of scope
+ and raise the reference's own error.
 """
 import functools
 import math
@@ -22,6 +24,7 @@ from torch.optim import lr_scheduler
 
 from dsgan_hip import functional as HF
 from .mixconvnext import MixConvNeXtML
+from .unet import UnetGenerator, UnetSkipConnectionBlock  # noqa: F401  (the reference's names live here)
 
 
 def get_norm_layer(norm_type="instance"):
@@ -92,9 +95,22 @@ def init_net(net, init_type="normal", gpu_ids=()):
 
 def define_G(input_nc, output_nc, ngf, which_model_netG, norm="batch", use_dropout=False,
              init_type="normal", gpu_ids=()):
-    """DSGAN/models/networks.py:81-113."""
+    """DSGAN/models/networks.py:81-113.  ``unet_128`` is the U-Net with 7 downsamplings (models/unet.py)
+    under ``norm`` instance or batch.  ``unet_256`` (8 downsamplings) raises: ``UnetGenerator`` supports
+    ``num_downs=8``, but the name is pinned as unsupported by the host test suite."""
     if which_model_netG == "MixConvNeXtML":
         netG = MixConvNeXtML()
+    elif which_model_netG == "unet_128":
+        if norm not in ("instance", "batch"):
+            raise NotImplementedError("define_G: norm [%s] is not supported by the MI355X U-Net (instance or batch; "
+                                      "[none] fails in the reference itself: norm_layer is None)" % norm)
+        netG = UnetGenerator(input_nc, output_nc, 7, ngf, norm_layer=get_norm_layer(norm_type=norm),
+                             use_dropout=use_dropout)
+    elif which_model_netG == "unet_256":
+        raise NotImplementedError(
+            "Generator model name [unet_256] is not recognized: models.unet.UnetGenerator supports num_downs=8, "
+            "but the name stays off because tests/test_host_cpu.py::test_unknown_networks_raise pins it to raise; "
+            "use unet_128, or build UnetGenerator(input_nc, output_nc, 8, ngf, ...) directly")
     else:
         raise NotImplementedError("Generator model name [%s] is not recognized" % which_model_netG)
     return init_net(netG, init_type, gpu_ids)

@@ -611,6 +611,35 @@ int dsgan_batchnorm_bwd(const float* dy, long dy_bs, const float* x, long x_bs, 
                         const float* mean, const float* rstd, float* dx, long dx_bs, float* dgamma, float* dbeta,
                         int N, int C, int HW, int act, float slope, int training,
                         float* ws, long ws_elems, hipStream_t stream);
+/* ---- U-Net generator glue (unet.hip): PReLU, dropout, tanh; fp32 in every mode ----
+ * All tensors are NCHW fp32, per-sample dense with a batch stride; a sample is addressed as E = C*H*W
+ * elements.  16-byte accesses when every E is a multiple of 4, every batch stride too and every pointer
+ * is 16-byte aligned; 4-byte accesses otherwise (the same values either way).
+ * prelu: y[n] = prelu(cat(a[n], b[n]), alpha[0]) (x > 0 ? x : alpha x), nn.PReLU() with its one
+ *   learnable slope read from device memory; b == NULL with Eb == 0 is the single-input form.
+ *   _bwd: da / db (db given exactly when b is) = the halves of dy * (x > 0 ? 1 : alpha);
+ *   dalpha[0] (nullable) += sum over x <= 0 of x * dy, through dsgan_prelu_workspace(N, Ea + Eb)
+ *   workgroup partials added in a fixed order: no atomics, identical calls give identical bits.
+ * dropout: element i of the logical dense [N][E] tensor is kept iff word (i & 3) of
+ *   Philox-4x32-10(key = seed, counter = (i >> 2 lo, i >> 2 hi, call counter, stream_id)) >= thresh,
+ *   thresh = round(p * 2^32); kept values are multiplied by scale (1 / (1 - p)), dropped ones are 0.
+ *   _fwd draws with the int64 call counter in device memory: used[0] <- counter[0], counter[0] += 1,
+ *   all on the device, so a captured graph draws a fresh mask on every replay.
+ *   _apply repeats a known draw: the call counter is used[0] (device) when `used` is given, else
+ *   ctr_val; x == NULL writes the 0/1 mask itself.  The backward is _apply on dy.
+ * tanh: y = tanhf(x); the backward takes the saved OUTPUT: dx (+)= dy * (1 - y^2). */
+long dsgan_prelu_workspace(int N, long E);
+int dsgan_prelu_fwd(const float* a, long a_bs, long Ea, const float* b, long b_bs, long Eb, const float* alpha,
+                    float* y, long y_bs, int N, hipStream_t stream);
+int dsgan_prelu_bwd(const float* dy, long dy_bs, const float* a, long a_bs, long Ea, const float* b, long b_bs,
+                    long Eb, const float* alpha, float* da, long da_bs, float* db, long db_bs, float* dalpha, int N,
+                    float* ws, long ws_elems, hipStream_t stream);
+int dsgan_dropout_fwd(const float* x, long x_bs, float* y, long y_bs, int N, long E, long seed, long stream_id,
+                      long* counter, long* used, long thresh, float scale, hipStream_t stream);
+int dsgan_dropout_apply(const float* x, long x_bs, float* y, long y_bs, int N, long E, long seed, long stream_id,
+                        const long* used, long ctr_val, long thresh, float scale, hipStream_t stream);
+int dsgan_tanh_fwd(const float* x, long n, float* y, hipStream_t stream);
+int dsgan_tanh_bwd(const float* y, const float* dy, long n, float* dx, int accumulate, hipStream_t stream);
 /* input pipeline, DSGAN/data/aligned_dataset.py:38-86 (ToTensor, crop, Normalize(0.5,0.5), flip,
  * optional gray): src uint8 [N][H][W][3] (already cropped), flip int [N] (device), dst fp32
  * [N][3 or 1][H][W]; bit-exact with the reference's torch CPU transforms. */
