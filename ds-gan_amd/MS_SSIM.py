@@ -10,7 +10,9 @@ pyramid) and the gradient flows to that operand.  SSIM is symmetric in (X, Y), s
 that requires grad is passed as the kernels' differentiated argument.  A gradient w.r.t. both
 operands at once is not implemented and raises (never a silent zero gradient); without any
 operand requiring grad, ``ms_ssim`` uses the evaluation kernel (per-image values for
-``size_average=False``).
+``size_average=False``).  ``ssim(size_average=False)`` and ``nonnegative_ssim=True`` are evaluation
+only (``HF.ssim_eval_affine``): with an operand that requires grad they raise.  ``SSIM`` / ``MS_SSIM``
+are the reference's ``nn.Module`` wrappers of the two functions.
 """
 import torch
 
@@ -39,7 +41,10 @@ def ssim(X, Y, data_range=255, size_average=True, win_size=11, win_sigma=1.5, wi
     if win is not None or win_size != 11 or win_sigma != 1.5 or tuple(K) != (0.01, 0.03):
         raise NotImplementedError("HIP ssim implements the default window (11, 1.5) and K=(0.01, 0.03)")
     if not size_average or nonnegative_ssim:
-        raise NotImplementedError("HIP ssim implements size_average=True without relu")
+        # per-image values / the relu'd per-channel form: evaluation only (HF.ssim_eval_affine)
+        if torch.is_grad_enabled() and (X.requires_grad or Y.requires_grad):
+            raise NotImplementedError("HIP ssim with a gradient implements size_average=True without relu")
+        return HF.ssim_eval_affine(X, Y, 1.0, 0.0, float(data_range), size_average, nonnegative_ssim)
     order = _grad_order(X, Y, "ssim")
     real, fake = order if order is not None else (X, Y)
     return HF.ssim_affine(real, fake, 1.0, 0.0, float(data_range))
@@ -64,3 +69,40 @@ def ms_ssim(X, Y, data_range=255, size_average=True, win_size=11, win_sigma=1.5,
         raise NotImplementedError("HIP ms_ssim gradient implements size_average=True (the batch mean)")
     real, fake = order
     return HF.ms_ssim_loss_affine(real, fake, 1.0, 0.0, float(data_range), w)
+
+
+class SSIM(torch.nn.Module):
+    """``ssim`` as a module with the reference's constructor arguments (DSGAN/MS_SSIM.py:228-268).
+    ``channel`` and ``spatial_dims`` only sized the reference's window tensor: the kernels build the
+    one 11-tap window themselves, so the module keeps (win_size, win_sigma) and the function refuses
+    anything but the default."""
+
+    def __init__(self, data_range=255, size_average=True, win_size=11, win_sigma=1.5, channel=3, spatial_dims=2,
+                 K=(0.01, 0.03), nonnegative_ssim=False):
+        super().__init__()
+        if spatial_dims != 2:
+            raise NotImplementedError("HIP SSIM supports 2 spatial dimensions")
+        self.data_range, self.size_average = data_range, size_average
+        self.win_size, self.win_sigma, self.channel = win_size, win_sigma, channel
+        self.K, self.nonnegative_ssim = K, nonnegative_ssim
+
+    def forward(self, X, Y):
+        return ssim(X, Y, data_range=self.data_range, size_average=self.size_average, win_size=self.win_size,
+                    win_sigma=self.win_sigma, K=self.K, nonnegative_ssim=self.nonnegative_ssim)
+
+
+class MS_SSIM(torch.nn.Module):
+    """``ms_ssim`` as a module with the reference's constructor arguments (DSGAN/MS_SSIM.py:271-311)."""
+
+    def __init__(self, data_range=255, size_average=True, win_size=11, win_sigma=1.5, channel=3, spatial_dims=2,
+                 weights=None, K=(0.01, 0.03)):
+        super().__init__()
+        if spatial_dims != 2:
+            raise NotImplementedError("HIP MS_SSIM supports 2 spatial dimensions")
+        self.data_range, self.size_average = data_range, size_average
+        self.win_size, self.win_sigma, self.channel = win_size, win_sigma, channel
+        self.weights, self.K = weights, K
+
+    def forward(self, X, Y):
+        return ms_ssim(X, Y, data_range=self.data_range, size_average=self.size_average, win_size=self.win_size,
+                       win_sigma=self.win_sigma, weights=self.weights, K=self.K)

@@ -16,6 +16,10 @@ void launch_split_reduce_multi(int n, const float* const* ws, const int* splits,
                                hipStream_t st);
 // out[0] = coef * sum_i part[i], i = 0..n-1 in a fixed order (losses.hip: the loss reductions' last pass)
 void launch_final_sum(const float* part, int n, float coef, float* out, hipStream_t st);
+// losses.hip's ssim_eval_kernel on (a*real+b, a*fake+b): tparts[plane][tile][2] = the (SSIM, cs) map sums
+// of each 32x32 output tile, tile = th * tiles_w + tw; returns the tiles per plane (evalimg.hip combines them)
+int launch_ssim_eval_tiles(const float* real, const float* fake, float a, float b, int planes, int H, int W,
+                           const float* win11, float C1, float C2, float* tparts, hipStream_t st);
 // wconv.hip's weight-grad partials [splits][T][M][C] -> dw[M][C][T] (+=), C % 32 == 0, T <= 16
 void launch_split_reduce_wconv(const float* ws, int splits, int T, int M, int C, float* dw, hipStream_t st);
 

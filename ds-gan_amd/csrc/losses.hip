@@ -414,6 +414,15 @@ __global__ __launch_bounds__(256) void ssim_eval_kernel(SSIMArgs s, int tiles_w,
   }
 }
 
+// one scale of ssim_eval_kernel for another unit (evalimg.hip's per-image SSIM), H, W >= 11
+int launch_ssim_eval_tiles(const float* real, const float* fake, float a, float b, int planes, int H, int W,
+                           const float* win11, float C1, float C2, float* tparts, hipStream_t st) {
+  SSIMArgs s{real, fake, a, b, planes, H, W, win11, C1, C2, nullptr, nullptr, nullptr, 0};
+  const int tw = (W - SS_K + SS_T) / SS_T, th = (H - SS_K + SS_T) / SS_T;
+  hipLaunchKernelGGL(ssim_eval_kernel, dim3(tw * th, planes), dim3(256), 0, st, s, tw, tparts);
+  return tw * th;
+}
+
 // F.avg_pool2d(a*x+b, 2, padding=(H%2, W%2)) with count_include_pad (divisor 4), :213-215
 __global__ void avgpool2_pad_kernel(const float* __restrict__ x, float* __restrict__ y, int planes, int H, int W,
                                     int Ho, int Wo, int ph, int pw, float a, float b) {

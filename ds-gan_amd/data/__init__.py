@@ -115,11 +115,12 @@ class CustomDatasetDataLoader:
     def name(self):
         return "CustomDatasetDataLoader"
 
-    def initialize(self, opt, isTrain):
+    def initialize(self, opt, isTrain, local=False):
         self.opt = opt
         self.dataset = CreateDataset(opt)
         shuffle = (not opt.serial_batches) if isTrain == "train" else False
-        rank, world = _dist()
+        # local: this process walks the whole dataset whatever the process group (the evaluation pass)
+        rank, world = (0, 1) if local else _dist()
         self.batch_sampler = None
         if world == 1:
             self.dataloader = torch.utils.data.DataLoader(
@@ -157,8 +158,8 @@ class CustomDatasetDataLoader:
                    "A_paths": data["A_paths"], "B_paths": data["B_paths"], "global_batch": gb}
 
 
-def CreateDataLoader(opt, isTrain="train"):
+def CreateDataLoader(opt, isTrain="train", local=False):
     data_loader = CustomDatasetDataLoader()
     print(data_loader.name())
-    data_loader.initialize(opt, isTrain)
+    data_loader.initialize(opt, isTrain, local)
     return data_loader

@@ -168,6 +168,12 @@ SIGNATURES = {
     "dsgan_ms_ssim_fwd_train": [P, P, F, F, I, I, I, I, P, F, F, P, I, P, L, P, P, S],
     "dsgan_ms_ssim_bwd": [P, P, F, F, I, I, I, I, P, F, F, P, I, P, L, P, P, P, I, S],
     "dsgan_ssim_bwd": [P, P, F, F, I, I, I, P, P, P, F, P, I, S],
+    # evalimg.hip
+    "dsgan_img_metrics_batch_parts": [I, I, I, I],
+    "dsgan_img_metrics_batch": [P, P, I, I, I, I, P, P, S],
+    "dsgan_images_to_u8": [P, I, P, I, P, I, I, I, I, P, S],
+    "dsgan_ssim_eval_parts": [I, I, I, I],
+    "dsgan_ssim_eval": [P, P, F, F, I, I, I, I, P, F, F, I, P, P, S],
     # lsgan.hip
     "dsgan_sigmoid_fwd": [P, L, P, S],
     "dsgan_sigmoid_bwd": [P, P, L, P, I, S],

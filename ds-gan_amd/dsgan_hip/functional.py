@@ -2550,6 +2550,62 @@ def ms_ssim_loss_affine(real, fake, a=0.5, b=0.5, data_range=1.0, weights=MS_SSI
 
 
 # ------------------------------------------------------------------------------------------
+# Test-set evaluation (evalimg.hip): no autograd, no host sync -- every call only enqueues work
+# ------------------------------------------------------------------------------------------
+
+def _eval4(*ts):
+    """Detached contiguous fp32 (N,C,H,W) operands of one shape."""
+    out = [t.detach().contiguous() for t in ts]
+    if any(t.dim() != 4 or t.dtype != torch.float32 or t.shape != out[0].shape for t in out):
+        raise ValueError("expected fp32 (N,C,H,W) tensors of one shape, got %s" % ([tuple(t.shape) for t in out],))
+    return out
+
+
+def img_metrics_batch(fake, real):
+    """[N,2] = (skimage-style SSIM, PSNR) of every image pair of two [N,C,H,W] batches in [-1, 1]:
+    per image what ``dsgan_img_metrics`` (util.metrics.TrainMetrics) computes for one."""
+    fake, real = _eval4(fake, real)
+    N, C, H, W = fake.shape
+    out = torch.empty((N, 2), device=fake.device, dtype=torch.float32)
+    n = _lib.load().dsgan_img_metrics_batch_parts(N, C, H, W)
+    part = torch.empty(max(n, 1), device=fake.device, dtype=torch.float64)
+    call("dsgan_img_metrics_batch", ptr(fake), ptr(real), N, C, H, W, ptr(part), ptr(out), stream())
+    return out
+
+
+def images_to_u8(*imgs):
+    """uint8 [N,H,k*W,3]: one to three [N,C,H,W] batches in [-1, 1] (C 1 or 3, a one-channel image
+    repeated to three) side by side as the reference's uint8 HWC images (train.py:110-128)."""
+    if not 1 <= len(imgs) <= 3:
+        raise ValueError("images_to_u8 takes one to three image batches")
+    imgs = [t.detach().contiguous() for t in imgs]
+    N, _, H, W = imgs[0].shape
+    for t in imgs:
+        if t.dim() != 4 or t.dtype != torch.float32 or (t.shape[0], t.shape[2], t.shape[3]) != (N, H, W):
+            raise ValueError("images_to_u8: fp32 (N,C,H,W) batches of one N, H, W required")
+    out = torch.empty((N, H, len(imgs) * W, 3), device=imgs[0].device, dtype=torch.uint8)
+    args = []
+    for i in range(3):
+        args += [ptr(imgs[i]), int(imgs[i].shape[1])] if i < len(imgs) else [None, 0]
+    call("dsgan_images_to_u8", *args, N, H, W, ptr(out), stream())
+    return out
+
+
+def ssim_eval_affine(real, fake, a=0.5, b=0.5, data_range=1.0, size_average=True, nonnegative=False):
+    """Gaussian SSIM of (a*real+b, a*fake+b) (DSGAN/MS_SSIM.py:95-150), evaluation only: the per-image
+    values [N] (channel mean of the plane means, relu'd per plane when ``nonnegative``) or their mean."""
+    real, fake = _eval4(real, fake)
+    N, C, H, W = real.shape
+    n = _lib.load().dsgan_ssim_eval_parts(N, C, H, W)
+    part = torch.empty(max(n, 1), device=real.device, dtype=torch.float32)
+    out = torch.empty(N + 1, device=real.device, dtype=torch.float32)
+    C1, C2 = (0.01 * data_range) ** 2, (0.03 * data_range) ** 2
+    call("dsgan_ssim_eval", ptr(real), ptr(fake), float(a), float(b), N, C, H, W, ptr(gauss_win(real.device)),
+         float(C1), float(C2), int(bool(nonnegative)), ptr(part), ptr(out), stream())
+    return out[N] if size_average else out[:N]
+
+
+# ------------------------------------------------------------------------------------------
 # LSGAN objective (--no_lsgan, quirk q3) and the multi-scale D's input pyramid (lsgan.hip)
 # ------------------------------------------------------------------------------------------
 

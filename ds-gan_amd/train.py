@@ -16,6 +16,11 @@ process group and drives cuda:LOCAL_RANK; ``--batchSize`` stays the GLOBAL batch
 rank trains its DataParallel-style chunk (data/__init__.py); the printed / CSV losses are the
 global-batch values (an all-reduce of the per-rank means at logging time); only rank 0 writes
 checkpoints and CSV files, behind a barrier.
+
+``--eval_freq N`` (default 0: off) with ``--eval_phase`` (default ``test_all/``): every N epochs rank 0
+scores the generator in eval mode on that split (evaluate.py's pass) and appends
+``[epoch, 'test', ssim_avg, psnr_avg]`` to ``each_epoch.csv`` after the ``train`` row; the pass leaves
+the training run bit-identical (``eval_pass``).
 """
 import argparse
 import csv
@@ -92,6 +97,26 @@ class NonfiniteMonitor:
         return "skipped " + " ".join("%s %d/%d" % (k, s, c) for k, (s, c) in rep.items()) + " "
 
 
+def eval_pass(model, opt, phase):
+    """(ssim_avg, psnr_avg) of the generator in eval mode over ``phase`` (evaluate.run_pass: batches in
+    order, no flip, no_grad; every module's ``training`` flag restored).  The pass leaves training as it
+    was: the loader's worker seed comes from the torch CPU generator and the dataset draws its crop
+    offsets from python ``random`` (which the ImagePool also uses), so both states are put back."""
+    from data import CreateDataLoader
+    from evaluate import eval_options, run_pass
+    from util.metrics import EvalMetrics
+    py_state, cpu_state = random.getstate(), torch.get_rng_state()
+    try:
+        dataset = CreateDataLoader(eval_options(opt, phase), "test", local=True).load_data()
+        metrics = EvalMetrics(model.device, max(len(dataset), 1))
+        run_pass(model.netG, dataset, opt.which_direction == "AtoB", len(dataset), metrics)
+        means = metrics.means()
+    finally:
+        random.setstate(py_state)
+        torch.set_rng_state(cpu_state)
+    return means[0], means[1]
+
+
 def main(argv=None, output_freq=100):
     from data import CreateDataLoader
     from models import create_model
@@ -101,6 +126,9 @@ def main(argv=None, output_freq=100):
     ap = argparse.ArgumentParser(add_help=False)
     ap.add_argument("--out", default=os.path.abspath(os.path.join("..", "resext50_vision1")))
     ap.add_argument("--dataroot", default="/root/dataset/256x256")
+    ap.add_argument("--eval_freq", type=int, default=0,
+                    help="every N epochs rank 0 scores the generator on --eval_phase (0: never)")
+    ap.add_argument("--eval_phase", default="test_all/", help="the split of the per-epoch test pass")
     known, rest = ap.parse_known_args(argv)
     rank, world, local = init_distributed()
     setup_seed(20)
@@ -153,6 +181,11 @@ def main(argv=None, output_freq=100):
         if rank == 0:
             with open(os.path.join(out, "each_epoch.csv"), "a", newline="") as f:
                 csv.writer(f).writerow([epoch, "train", ssim_avg, psnr_avg])
+            if known.eval_freq > 0 and epoch % known.eval_freq == 0:   # the other ranks wait at the barrier below
+                t_ssim, t_psnr = eval_pass(model, opt, known.eval_phase)
+                print("test (%s) ssim: %.4f psnr: %.3f" % (known.eval_phase, t_ssim, t_psnr))
+                with open(os.path.join(out, "each_epoch.csv"), "a", newline="") as f:
+                    csv.writer(f).writerow([epoch, "test", t_ssim, t_psnr])
             print("saving the model at the end of epoch %d, iters %d" % (epoch, i + 1))
             model.save_networks(epoch)
             print("End of epoch %d / %d \t Time Taken: %d sec" % (epoch, opt.niter + opt.niter_decay,

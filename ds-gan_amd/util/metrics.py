@@ -27,3 +27,55 @@ class TrainMetrics:
         s, p, n = self.acc.tolist()
         n = max(n, 1.0)
         return s / n, p / n
+
+
+class EvalMetrics:
+    """Per-image test-set metrics in a preallocated device buffer of ``capacity`` rows (evaluate.py,
+    train.py --eval_freq).  A row is COLUMNS:
+
+      ssim        the skimage-style SSIM train.py logs (uint8 images, uniform 7x7 window)
+      psnr        of the same uint8 images
+      ssim_gauss  MS_SSIM.ssim of (t+1)/2 with data_range 1 (11-tap gaussian window)
+      ms_ssim     MS_SSIM.ms_ssim of the same; NaN when the smaller side is <= 160
+
+    ``update`` only enqueues kernels (no .item(), .cpu() or synchronize; it can be captured in a HIP
+    graph); ``rows`` and ``means`` read the buffer back once."""
+
+    COLUMNS = ("ssim", "psnr", "ssim_gauss", "ms_ssim")
+    MS_MIN_SIDE = 160   # (win_size - 1) * 2^4, DSGAN/MS_SSIM.py:194-197
+
+    def __init__(self, device, capacity):
+        self.buf = torch.full((int(capacity), len(self.COLUMNS)), float("nan"), device=device, dtype=torch.float32)
+        self.n = 0
+
+    def reset(self):
+        self.n = 0
+
+    def update(self, fake, real):
+        """fake, real: [N,C,H,W] batches in [-1, 1]; appends one row per image."""
+        from dsgan_hip import functional as HF
+        N, _, H, W = fake.shape
+        if self.n + N > self.buf.shape[0]:
+            raise ValueError("EvalMetrics: %d rows of capacity, %d images" % (self.buf.shape[0], self.n + N))
+        rows = self.buf[self.n:self.n + N]
+        both = HF.img_metrics_batch(fake, real)
+        rows[:, 0:2].copy_(both)
+        if min(H, W) > 10:
+            rows[:, 2].copy_(HF.ssim_eval_affine(real, fake, 0.5, 0.5, 1.0, size_average=False))
+        else:   # smaller than the 11-tap window
+            rows[:, 2].fill_(float("nan"))
+        if min(H, W) > self.MS_MIN_SIDE:
+            rows[:, 3].copy_(HF.ms_ssim_affine(real, fake, 0.5, 0.5, 1.0, size_average=False))
+        else:
+            rows[:, 3].fill_(float("nan"))
+        self.n += N
+
+    def rows(self):
+        """The rows so far as a list of [ssim, psnr, ssim_gauss, ms_ssim] lists (one read-back)."""
+        return self.buf[:self.n].cpu().tolist()
+
+    def means(self):
+        """Column means over the rows so far (NaN for a column that holds NaN, or without rows)."""
+        if self.n == 0:
+            return [float("nan")] * len(self.COLUMNS)
+        return self.buf[:self.n].double().mean(0).cpu().tolist()

@@ -650,6 +650,28 @@ int dsgan_u8_to_image(const unsigned char* src, const int* flip, float* dst, int
  * conversion; part = 128 doubles of scratch.  No host sync. */
 int dsgan_img_metrics(const float* fake, const float* real, int C, int H, int W, double* part, float* acc,
                       hipStream_t stream);
+/* ---- test-set evaluation (evalimg.hip): evaluate.py / util/metrics.py EvalMetrics ----
+ * img_metrics_batch: out (float [N][2]) = {skimage-SSIM, PSNR} of every pair (fake[n], real[n]) of dense
+ *   [N][C][H][W] batches in [-1,1], each value as one dsgan_img_metrics call defines it (uint8 conversion,
+ *   uniform 7x7 window, sample covariance, data range 255, map cropped by 3, channel mean; PSNR 100 when
+ *   mse/255^2 < 1e-10).  H, W > 6.  part: dsgan_img_metrics_batch_parts DOUBLES of scratch, one
+ *   (sum S, sum err^2) pair per (image, channel, 32x32 tile), added per image in a fixed order: identical
+ *   calls give identical bits and an image's values do not depend on its place in the batch or on N.
+ * images_to_u8: the k non-NULL images of (a, b, c), dense fp32 [N][Ci][H][W] with Ci in {1, 3}, side by
+ *   side as uint8 [N][H][k*W][3] (np.hstack of the reference's uint8 HWC images, DSGAN/train.py:110-128):
+ *   trunc(clip(((t+1)/2)*255, 0, 255)), a one-channel image repeated to three, NaN -> 0.
+ * ssim_eval: gaussian SSIM (DSGAN/MS_SSIM.py:95-150) of (a*real+b, a*fake+b) per image: out[n] = the mean
+ *   over the channels of the plane means of the SSIM map (each relu'd first when nonneg, :144-145),
+ *   out[N] = the batch mean.  H, W >= 11.  part: dsgan_ssim_eval_parts floats of scratch. */
+long dsgan_img_metrics_batch_parts(int N, int C, int H, int W);
+int dsgan_img_metrics_batch(const float* fake, const float* real, int N, int C, int H, int W, double* part,
+                            float* out, hipStream_t stream);
+int dsgan_images_to_u8(const float* a, int Ca, const float* b, int Cb, const float* c, int Cc, int N, int H, int W,
+                       unsigned char* out, hipStream_t stream);
+long dsgan_ssim_eval_parts(int N, int C, int H, int W);
+int dsgan_ssim_eval(const float* real, const float* fake, float a, float b, int N, int C, int H, int W,
+                    const float* win11, float C1, float C2, int nonneg, float* part, float* out,
+                    hipStream_t stream);
 /* MS-SSIM evaluation of (a*real+b, a*fake+b), DSGAN/MS_SSIM.py:153-225 (ms_ssim, forward only;
  * the differentiable form is dsgan_ms_ssim_fwd_train + dsgan_ms_ssim_bwd below): per scale the SSIM / contrast-structure plane means, then the padded 2x2 average pool;
  * weights_host = the level weights (host array, levels <= 8).  work: dsgan_ms_ssim_workspace
