@@ -354,7 +354,6 @@ __global__ __launch_bounds__(BN_NT) void bn_bwd_apply(BNBwdArgs a, const float* 
   }
 }
 
-static inline bool bn_al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 }  // namespace dsg
 
@@ -406,7 +405,7 @@ int dsgan_batchnorm_fwd(const float* x, long x_bs, const float* gamma, const flo
               "dsgan_batchnorm_fwd: mean / rstd may not alias the running buffers");
   const BNPlan p = bn_plan(N, C, HW);
   DSG_WS(p.need, ws, ws_elems, "dsgan_batchnorm_fwd");
-  const bool v4 = HW % 4 == 0 && x_bs % 4 == 0 && y_bs % 4 == 0 && bn_al16(x) && bn_al16(y);
+  const bool v4 = HW % 4 == 0 && x_bs % 4 == 0 && y_bs % 4 == 0 && al16(x) && al16(y);
   BNFwdArgs a{x, x_bs, gamma, beta, y, y_bs, mean, rstd, running_mean, running_var, num_batches_tracked,
               N, C, HW, act, slope, eps, momentum, training ? 1 : 0};
   if (!training) {
@@ -433,8 +432,8 @@ int dsgan_batchnorm_bwd(const float* dy, long dy_bs, const float* x, long x_bs, 
   DSG_REQUIRE(!training || (long)N * HW > 1, "dsgan_batchnorm_bwd: N*HW == 1 in training mode");
   const BNPlan p = bn_plan(N, C, HW);
   DSG_WS(p.need, ws, ws_elems, "dsgan_batchnorm_bwd");
-  const bool v4 = HW % 4 == 0 && dy_bs % 4 == 0 && x_bs % 4 == 0 && dx_bs % 4 == 0 && bn_al16(dy) && bn_al16(x) &&
-                  bn_al16(dx);
+  const bool v4 = HW % 4 == 0 && dy_bs % 4 == 0 && x_bs % 4 == 0 && dx_bs % 4 == 0 && al16(dy) && al16(x) &&
+                  al16(dx);
   BNBwdArgs a{dy, dy_bs, x, x_bs, gamma, beta, mean, rstd, dx, dx_bs, dgamma, dbeta,
               N, C, HW, act, slope, training ? 1 : 0};
   if (p.form == 0) {

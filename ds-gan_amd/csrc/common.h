@@ -14,8 +14,9 @@ void launch_split_reduce_kk(const float* ws, int splits, long MN, float* dw, flo
 // and the deferred mode that queues them for one batched flush)
 void launch_split_reduce_multi(int n, const float* const* ws, const int* splits, const long* MN, float* const* dw,
                                hipStream_t st);
-// out[0] = coef * sum_i part[i], i = 0..n-1 in a fixed order (losses.hip: the loss reductions' last pass)
-void launch_final_sum(const float* part, int n, float coef, float* out, hipStream_t st);
+// out[0] = coef * sum_i part[i], i = 0..n-1 in a fixed order (losses.hip: the loss reductions' last pass).
+// part is the caller's scratch: the call may overwrite it (many partials are summed in place, in two levels).
+void launch_final_sum(float* part, int n, float coef, float* out, hipStream_t st);
 // losses.hip's ssim_eval_kernel on (a*real+b, a*fake+b): tparts[plane][tile][2] = the (SSIM, cs) map sums
 // of each 32x32 output tile, tile = th * tiles_w + tw; returns the tiles per plane (evalimg.hip combines them)
 int launch_ssim_eval_tiles(const float* real, const float* fake, float a, float b, int planes, int H, int W,
@@ -285,6 +286,22 @@ __device__ __forceinline__ float block_sum(float v, float* sh) {
   return r;
 }
 
+// ---- raw buffer loads --------------------------------------------------------------------
+// A raw (unstrided, unswizzled) buffer resource over `range` bytes at `base`: a load whose byte offset is
+// at or past the range returns 0, which is how the kernels read image borders and ragged tails without
+// a branch.  kBufRsrcFlags is word 3 of the resource: DATA_FORMAT = 32 (bits 15-18), everything else 0.
+constexpr int kBufRsrcFlags = 0x00020000;
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const void* base, unsigned range) {
+  return __builtin_amdgcn_make_buffer_rsrc((void*)base, (short)0, range, kBufRsrcFlags);
+}
+// one float / one float4 at byte offset `off` (no scalar offset, default cache policy)
+__device__ __forceinline__ float buf_ld(__amdgpu_buffer_rsrc_t r, unsigned off) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)off, 0, 0));
+}
+__device__ __forceinline__ float4 buf_ld4(__amdgpu_buffer_rsrc_t r, unsigned off) {
+  return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0));
+}
+
 }  // namespace dsg
 
 // ---- error plumbing for the C ABI -------------------------------------------------
@@ -309,6 +326,25 @@ void dsgan_set_error(const char* fmt, ...);
   } while (0)
 
 static inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1) / b); }
+
+// p is 16-byte aligned; with a batch stride `bs` (4-byte elements), so is every sample's base
+static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+static inline bool al16(const void* p, long bs) { return (bs & 3) == 0 && al16(p); }
+// Grids of the 256-thread grid-stride elementwise kernels over n elements: capped at 16384 workgroups,
+// or (grid_for) at 65535 * 8.  The reduction launchers size their own grids: there the grid is the number
+// of block partials, so it fixes the order of additions.
+static inline unsigned ew_grid(long n) {
+  long g = (n + 255) / 256;
+  if (g > 16384) g = 16384;
+  if (g < 1) g = 1;
+  return (unsigned)g;
+}
+static inline unsigned grid_for(long n, int bs = 256) {
+  long g = (n + bs - 1) / bs;
+  if (g > 65535L * 8) g = 65535L * 8;
+  if (g < 1) g = 1;
+  return (unsigned)g;
+}
 
 // ---- scratch (workspace) contract -------------------------------------------------
 // Every entry point that takes a scratch buffer also takes its size `ws_elems` (fp32 elements, or

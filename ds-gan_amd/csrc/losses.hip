@@ -121,10 +121,10 @@ __global__ __launch_bounds__(256) void strided_sum_kernel(const float* __restric
 }
 
 constexpr int FS_TWO_LEVEL = 16384, FS_CHUNK = 1024;
-void launch_final_sum(const float* part, int n, float coef, float* out, hipStream_t st) {
+void launch_final_sum(float* part, int n, float coef, float* out, hipStream_t st) {
   if (n > FS_TWO_LEVEL) {   // (the partials are the caller's scratch: overwritten in place)
     const int nc = (n + FS_CHUNK - 1) / FS_CHUNK;
-    hipLaunchKernelGGL(chunk_sum_kernel, dim3((unsigned)nc), dim3(256), 0, st, const_cast<float*>(part), n, FS_CHUNK);
+    hipLaunchKernelGGL(chunk_sum_kernel, dim3((unsigned)nc), dim3(256), 0, st, part, n, FS_CHUNK);
     hipLaunchKernelGGL(strided_sum_kernel, dim3(1), dim3(256), 0, st, part, nc, FS_CHUNK, coef, out);
     return;
   }

@@ -8,13 +8,6 @@
 
 namespace dsg {
 
-static inline unsigned ew_grid(long n) {
-  long g = (n + 255) / 256;
-  if (g > 16384) g = 16384;
-  if (g < 1) g = 1;
-  return (unsigned)g;
-}
-
 // ---- sigmoid -------------------------------------------------------------------------------
 // The accurate expf: this value is a loss input, not a gate.  expf(-x) overflows to +inf for
 // x < -88.7 (y = 0) and underflows to 0 for x > 103 (y = 1): finite either way.
@@ -91,13 +84,6 @@ __global__ __launch_bounds__(256) void avgpool3s2_fwd_kernel(const float* __rest
 
 constexpr unsigned AP_OOB = 0xFFFFFFF0u;   // past every buffer range: the load returns 0
 
-__device__ __forceinline__ float ap_ld(__amdgpu_buffer_rsrc_t r, unsigned off) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)off, 0, 0));
-}
-__device__ __forceinline__ float4 ap_ld4(__amdgpu_buffer_rsrc_t r, unsigned off) {
-  return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0));
-}
-
 // Fast form (W % 8 == 0, 16-byte aligned rows on both sides, C*H*W*4 < 2^31): one lane produces 4
 // adjacent outputs of a row from three input rows, each row read as two 16-byte loads (columns
 // 2wo0 .. 2wo0+7) plus the halo column 2wo0-1.  Rows and the halo column outside the image take
@@ -113,8 +99,7 @@ __global__ __launch_bounds__(256) void avgpool3s2_fwd_v4_kernel(const float* __r
     const int n = (int)(i / per);
     const long r = i - n * per;
     const int q = (int)(r % Wq), ho = (int)((r / Wq) % Ho), c = (int)(r / ((long)Wq * Ho));
-    const __amdgpu_buffer_rsrc_t rx =
-        __builtin_amdgcn_make_buffer_rsrc((void*)(x + n * x_bs), (short)0, range, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = buf_rsrc(x + n * x_bs, range);
     const int wo0 = 4 * q;
     float4 lo[3], hi[3];
     float hl[3];
@@ -123,9 +108,9 @@ __global__ __launch_bounds__(256) void avgpool3s2_fwd_v4_kernel(const float* __r
       const int h = 2 * ho - 1 + a;
       const bool in = h >= 0 && h < H;
       const unsigned off = (unsigned)((((long)c * H + h) * W + 2 * wo0) * 4);
-      lo[a] = ap_ld4(rx, in ? off : AP_OOB);
-      hi[a] = ap_ld4(rx, in ? off + 16u : AP_OOB);
-      hl[a] = ap_ld(rx, in && wo0 > 0 ? off - 4u : AP_OOB);
+      lo[a] = buf_ld4(rx, in ? off : AP_OOB);
+      hi[a] = buf_ld4(rx, in ? off + 16u : AP_OOB);
+      hl[a] = buf_ld(rx, in && wo0 > 0 ? off - 4u : AP_OOB);
     }
     const int rc = taps_in(ho, H);
     float4 o;

@@ -18,6 +18,7 @@
 // Weights are bf16 copies (w1 [4C][C] as nn.Linear stores it, w2 [P][4C]); the same two LDS
 // chunk layouts serve the transposed products of the backward through the transposing LDS read.
 #include "common.h"
+#include "lds_dma.h"
 #include <type_traits>
 
 namespace dsg {
@@ -256,22 +257,6 @@ __device__ __forceinline__ void wch_store_swz(const mu32x4 (&r1)[N1], const mu32
   }
 }
 
-// One 16-byte-per-lane LDS-DMA (global_load_lds_dwordx4): lane l's 16 bytes land at LDS byte
-// address lds + 16 l.  Issued from asm so that hipcc neither counts it nor drains it with a
-// vmcnt(0) in front of every LDS read of the other buffer: completion is waited for by hand
-// (s_waitcnt vmcnt + barrier before the buffer is read).  M0 is written and restored in the same
-// statement (it is compiler-reserved).
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(gsrc), "s"(lds)
-               : "memory");
-}
-__device__ __forceinline__ unsigned lds_addr(const void* p) {   // LDS byte offset of a __shared__ pointer
-  return __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)p);
-}
-
 // Weight chunk j -> LDS by LDS-DMA (no register staging): W1 rows [j*64, +64) as [64][C] (in qswap
 // row order when QS), W2 columns [j*64, +64) as [P][64].  Every wave issues C/64 + P/64 wave-instructions
 // of 1 KB each; the LDS image of one instruction is lane-linear, the swizzle is applied on the
@@ -288,14 +273,14 @@ __device__ __forceinline__ void glds_chunk(void* W1d, void* W2d, const void* w1v
   for (int i = 0; i < N1; ++i) {
     const int inst = wave * N1 + i, r = inst * R1 + lane / S1, ps = lane % S1;
     const unsigned short* src = w1 + ((long)j * 64 + (QS ? qswap(r) : r)) * C + (ps ^ slot_swz<S1>(r)) * 8;
-    glds16(src, lds_addr(W1h + inst * 512));
+    dma16(src, lds_off(W1h + inst * 512));
   }
   constexpr int N2 = P / 8 / NW;
 #pragma unroll
   for (int i = 0; i < N2; ++i) {
     const int inst = wave * N2 + i, r = inst * 8 + lane / 8, ps = lane % 8;
     const unsigned short* src = w2 + (long)r * (4 * C) + j * 64 + (ps ^ slot_swz<8>(r)) * 8;
-    glds16(src, lds_addr(W2h + inst * 512));
+    dma16(src, lds_off(W2h + inst * 512));
   }
 }
 
@@ -1093,9 +1078,9 @@ __global__ __launch_bounds__(256, 1) void mlp_bwd_dma_kernel(MlpArgs g) {
     unsigned short* const W1h = (unsigned short*)W1d;
     unsigned short* const W2h = W1h + W1_SZ;
 #pragma unroll
-    for (int i = 0; i < N1; ++i) glds16(w1 + ((unsigned)(j * 64 * C) + o1[i]), lds_addr(W1h + (wave * N1 + i) * 512));
+    for (int i = 0; i < N1; ++i) dma16(w1 + ((unsigned)(j * 64 * C) + o1[i]), lds_off(W1h + (wave * N1 + i) * 512));
 #pragma unroll
-    for (int i = 0; i < N2; ++i) glds16(w2 + ((unsigned)(j * 64) + o2[i]), lds_addr(W2h + (wave * N2 + i) * 512));
+    for (int i = 0; i < N2; ++i) dma16(w2 + ((unsigned)(j * 64) + o2[i]), lds_off(W2h + (wave * N2 + i) * 512));
   };
 
   chunk_dma(0, Wslot0);

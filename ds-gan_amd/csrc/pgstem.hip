@@ -24,12 +24,6 @@ namespace dsg {
 typedef __attribute__((ext_vector_type(2))) float pg_f2;
 constexpr unsigned PG_OOB = 0xFFFFFFF0u;
 
-__device__ __forceinline__ float pg_ld(__amdgpu_buffer_rsrc_t r, unsigned off) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)off, 0, 0));
-}
-__device__ __forceinline__ float4 pg_ld4(__amdgpu_buffer_rsrc_t r, unsigned off) {
-  return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0));
-}
 __device__ __forceinline__ float pg_lrelu(float v, float slope) { return v > 0.f ? v : v * slope; }
 
 // ---- forward ----------------------------------------------------------------------------------
@@ -70,7 +64,7 @@ __global__ __launch_bounds__(256, 2) void pgs_fwd_kernel(const float* __restrict
       for (int k = 0; k < 8; ++k) wa[mb][ci][k] = w[((32 * mb + lr) * CI + ci) * 16 + 8 * lh + k];
 
   const int spi = Ho >> 1, stages = nb * spi, ntile = Wo >> 4;   // 32-position tiles per stage
-  const __amdgpu_buffer_rsrc_t rxa = __builtin_amdgcn_make_buffer_rsrc((void*)x, (short)0, 0xFFFFFFF0u, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rxa = buf_rsrc(x, 0xFFFFFFF0u);
   // persistent over stages: the next stage's input rows are loaded into registers before this
   // stage's MFMAs (a one-stage-per-workgroup grid runs every workgroup's load, MFMA and store
   // phases in lockstep: HBM idles while the MFMAs run)
@@ -85,7 +79,7 @@ __global__ __launch_bounds__(256, 2) void pgs_fwd_kernel(const float* __restrict
       const int i = tid + 256 * u, ix4 = i % W4, q = i / W4, rr = q % 6, ci = q / 6;
       const int iy = 2 * oy_ - 1 + rr;
       const bool ok = i < nx && (unsigned)iy < (unsigned)H;
-      v[u] = pg_ld4(rxa, ok ? (unsigned)((xb + (long)ci * H * W + (long)iy * W + 4 * ix4) * 4) : PG_OOB);
+      v[u] = buf_ld4(rxa, ok ? (unsigned)((xb + (long)ci * H * W + (long)iy * W + 4 * ix4) * 4) : PG_OOB);
     }
   };
   if (blockIdx.x < stages) load_stage(blockIdx.x);
@@ -253,8 +247,7 @@ __global__ __launch_bounds__(256, 2) void pgs_wgrad_kernel(PgWArgs a) {
         }
       }
       // (branch-free: a guarded load would be branched around and drain vmcnt per element)
-      const __amdgpu_buffer_rsrc_t rxb = __builtin_amdgcn_make_buffer_rsrc(
-          (void*)(a.x + (long)b * a.x_bs), (short)0, (unsigned)(CI * H * W * 4), 0x00020000);
+      const __amdgpu_buffer_rsrc_t rxb = buf_rsrc(a.x + (long)b * a.x_bs, (unsigned)(CI * H * W * 4));
       const int W4 = W >> 2, nx = CI * 6 * W4;
       for (int i0 = tid; i0 < nx; i0 += 256 * 8) {
         float4 v[8];
@@ -263,7 +256,7 @@ __global__ __launch_bounds__(256, 2) void pgs_wgrad_kernel(PgWArgs a) {
           const int i = i0 + 256 * u, ix4 = i % W4, q = i / W4, rr = q % 6, ci = q / 6;
           const int iy = 2 * oy0 - 1 + rr;
           const bool ok = i < nx && (unsigned)iy < (unsigned)H;
-          v[u] = pg_ld4(rxb, ok ? (unsigned)((ci * H * W + iy * W + 4 * ix4) * 4) : PG_OOB);
+          v[u] = buf_ld4(rxb, ok ? (unsigned)((ci * H * W + iy * W + 4 * ix4) * 4) : PG_OOB);
         }
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
@@ -353,10 +346,11 @@ __global__ __launch_bounds__(256) void pgs_dgrad_kernel(const float* __restrict_
     __syncthreads();
     // branch-free loads (a guarded load would be branched around and drain vmcnt per element)
     const unsigned rng = (unsigned)(32 * HWo * 4);
+    // (the builtin, not buf_rsrc: through the helper this kernel's schedule came out different)
     const __amdgpu_buffer_rsrc_t rdy = __builtin_amdgcn_make_buffer_rsrc((void*)(dy + (long)b * dy_bs + c0 * HWo),
-                                                                         (short)0, rng, 0x00020000);
+                                                                         (short)0, rng, kBufRsrcFlags);
     const __amdgpu_buffer_rsrc_t ryy = __builtin_amdgcn_make_buffer_rsrc((void*)(y + (long)b * y_bs + c0 * HWo),
-                                                                         (short)0, rng, 0x00020000);
+                                                                         (short)0, rng, kBufRsrcFlags);
     constexpr int NI = 32 * TR * C4;       // interior 16-byte items, 8 in flight per lane
     for (int k0 = tid; k0 < NI; k0 += 256 * 8) {
       float4 gv[8], yv[8];
@@ -366,8 +360,8 @@ __global__ __launch_bounds__(256) void pgs_dgrad_kernel(const float* __restrict_
         const int oy = i0 - 1 + rr;
         const unsigned o = k < NI && (unsigned)oy < (unsigned)Ho ? (unsigned)((co * HWo + oy * Wo + j0 + 4 * c4) * 4)
                                                                  : PG_OOB;
-        gv[u] = pg_ld4(rdy, o);
-        yv[u] = pg_ld4(ryy, o);
+        gv[u] = buf_ld4(rdy, o);
+        yv[u] = buf_ld4(ryy, o);
       }
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
@@ -387,7 +381,7 @@ __global__ __launch_bounds__(256) void pgs_dgrad_kernel(const float* __restrict_
       const int oy = i0 - 1 + rr, ox = side ? j0 + CB : j0 - 1;
       const unsigned o = (unsigned)oy < (unsigned)Ho && (unsigned)ox < (unsigned)Wo
                              ? (unsigned)((co * HWo + oy * Wo + ox) * 4) : PG_OOB;
-      const float g = pg_ld(rdy, o), yy = pg_ld(ryy, o);
+      const float g = buf_ld(rdy, o), yy = buf_ld(ryy, o);
       dt[co * CS + rr * TCP + (side ? CB + 4 : 3)] = yy > 0.f ? g : g * slope;
     }
     __syncthreads();

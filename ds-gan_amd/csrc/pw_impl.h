@@ -147,16 +147,16 @@ __device__ __forceinline__ void pw_fd_epi(const PwArgs& g, pf32x16 (&acc)[TM][TN
   const unsigned range = grange;
 #endif
   const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(ybase + (long)bimg * ybs + p0), (short)0, range, 0x00020000);
+      (void*)(ybase + (long)bimg * ybs + p0), (short)0, range, kBufRsrcFlags);
   const __amdgpu_buffer_rsrc_t ryh = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)((T16*)g.Y + (long)bimg * g.y_bs + p0), (short)0, range / 2, 0x00020000);
+      (void*)((T16*)g.Y + (long)bimg * g.y_bs + p0), (short)0, range / 2, kBufRsrcFlags);
   __amdgpu_buffer_rsrc_t rp = ry, rg = ry;
   // bf16 side tensors (gbf): same element offsets, byte offsets halved
   const int esz = gbf ? 2 : 4;
   if (ypre) rp = __builtin_amdgcn_make_buffer_rsrc((void*)((char*)ypre + ((long)bimg * g.ypre_bs + p0) * esz), (short)0,
-                                                   gbf ? range / 2 : range, 0x00020000);
+                                                   gbf ? range / 2 : range, kBufRsrcFlags);
   if (gpre) rg = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)gpre + ((long)bimg * g.gpre_bs + p0) * esz),
-                                                   (short)0, gbf ? grange / 2 : grange, 0x00020000);
+                                                   (short)0, gbf ? grange / 2 : grange, kBufRsrcFlags);
   // 16-bit store of this lane's 16 values: groups (q, q+1) swap halves so lanes 0-31 hold pixels
   // 8q..8q+7 and lanes 32-63 pixels 8q+8..8q+15 of their channel (byte offset +16)
   auto store16 = [&](__amdgpu_buffer_rsrc_t r, const float* v, int vh, int srow) __attribute__((always_inline)) {
@@ -444,9 +444,11 @@ __global__ __launch_bounds__(128 * WN, WN == 2 ? 2 : 1) void pwgemm_kernel(PwArg
   // around the load by the compiler; see igemm.hip ldsel.)
   const int b_fix = (MODE == PW_WGRAD) ? 0 : bimg;
   const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)g.A, (short)0, g.a_range, 0x00020000);
+      (void*)g.A, (short)0, g.a_range, kBufRsrcFlags);
   const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)((const char*)g.B + (long)b_fix * g.b_bs * (BBF ? 2 : 4)), (short)0, g.b_range, 0x00020000);
+      (void*)((const char*)g.B + (long)b_fix * g.b_bs * (BBF ? 2 : 4)), (short)0, g.b_range, kBufRsrcFlags);
+  // (this file keeps the builtin constructor and its own load lambdas: through common.h's buf_rsrc /
+  // buf_ld4 the register allocation of the wide kernels came out different)
   auto bld4 = [](__amdgpu_buffer_rsrc_t r, unsigned voff) {
     return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, 0, 0));
   };
@@ -628,7 +630,7 @@ __global__ __launch_bounds__(128 * WN, WN == 2 ? 2 : 1) void pwgemm_kernel(PwArg
     if (gpf_on) {
       const unsigned grange = (unsigned)(((long)g.M * g.P - p0) * 2);
       const __amdgpu_buffer_rsrc_t rgp = __builtin_amdgcn_make_buffer_rsrc(
-          (void*)((const char*)g.gpre + ((long)bimg * g.gpre_bs + p0) * 2), (short)0, grange, 0x00020000);
+          (void*)((const char*)g.gpre + ((long)bimg * g.gpre_bs + p0) * 2), (short)0, grange, kBufRsrcFlags);
 #pragma unroll
       for (int j = 0; j < TN; ++j)
 #pragma unroll
@@ -998,7 +1000,6 @@ static int wgrad_cfg(PwArgs& g, bool any_bf16, int* bm) {
   return wgrad_plan(g.M, g.N, g.K, *bm, 128, PBK, 640, &g.k_split);
 }
 
-static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // 256-row M tiles for the wide, deep FWD / DGRAD GEMMs: each staged pixel tile feeds twice the
 // MFMAs, as long as the grid still keeps >= 2 workgroups per CU.  Isolated A/B at the step's

@@ -73,12 +73,8 @@ __global__ __launch_bounds__(256, 2) void pwf32_kernel(PfArgs g) {
   // Operand loads are 16-byte buffer loads; an element outside its tensor gets an offset past
   // the resource range and reads 0 in hardware (no branch, no select -- see pwgemm.hip).
   constexpr unsigned OOB = 0xFFFFFFF0u;
-  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)g.A, (short)0, g.a_range, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(g.B + (MODE == PF_WGRAD ? 0L : (long)bimg * g.b_bs)), (short)0, g.b_range, 0x00020000);
-  auto bld = [](__amdgpu_buffer_rsrc_t r, unsigned off) {
-    return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0));
-  };
+  const __amdgpu_buffer_rsrc_t rA = buf_rsrc(g.A, g.a_range);
+  const __amdgpu_buffer_rsrc_t rB = buf_rsrc((void*)(g.B + (MODE == PF_WGRAD ? 0L : (long)bimg * g.b_bs)), g.b_range);
   float4 ra[A_ITEMS], rb[B_ITEMS];
   float asr[A_ITEMS];   // WGRAD asum: this thread's running row sums of its A items (fixed order)
 #pragma unroll
@@ -103,7 +99,7 @@ __global__ __launch_bounds__(256, 2) void pwf32_kernel(PfArgs g) {
         off = (m < g.M && kb + (it & 3) * 4 < kend)
                   ? (bw * (unsigned)g.a_bs + (unsigned)m * g.P + pw + (it & 3) * 4) * 4u : OOB;
       }
-      ra[i] = bld(rA, off);
+      ra[i] = buf_ld4(rA, off);
     }
 #pragma unroll
     for (int i = 0; i < B_ITEMS; ++i) {
@@ -117,7 +113,7 @@ __global__ __launch_bounds__(256, 2) void pwf32_kernel(PfArgs g) {
         off = (n < g.N && kb + (it & 3) * 4 < kend)
                   ? (bw * (unsigned)g.b_bs + (unsigned)n * g.P + pw + (it & 3) * 4) * 4u : OOB;
       }
-      rb[i] = bld(rB, off);
+      rb[i] = buf_ld4(rB, off);
     }
   };
   auto sstore = [&](int buf) {

@@ -30,10 +30,6 @@ struct SkArgs {
   int act; float slope;   // small_in only
 };
 
-__device__ __forceinline__ float bld(__amdgpu_buffer_rsrc_t r, unsigned off) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)off, 0, 0));
-}
-
 // out[b][m][oh][ow] (+)= bias[m] + sum_{k,kh,kw} w(m,k,kh,kw) * in(b, k, tap)
 //   conv:        in = x[b][k][oh*s - pad + kh][ow*s - pad + kw]
 //   transposed:  in = x[b][k][(oh + pad - kh)/s][(ow + pad - kw)/s]  (when divisible)
@@ -75,7 +71,7 @@ __global__ __launch_bounds__(64 * NWV) void small_out_kernel(SkArgs a) {
     const int b = (int)(q / HWo), r = (int)(q - (long)b * HWo);
     const int oh = r / a.Wo, ow = r - (r / a.Wo) * a.Wo;
     const int HWi = a.Hin * a.Win;
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, (short)0, a.x_range, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = buf_rsrc(a.x, a.x_range);
     const unsigned xb = (unsigned)((long)b * a.x_bs);
 
     // per-tap in-plane offsets (or OOB), independent of k
@@ -116,7 +112,7 @@ __global__ __launch_bounds__(64 * NWV) void small_out_kernel(SkArgs a) {
       if (KH_) {
         float xv[TMAX];
 #pragma unroll
-        for (int t = 0; t < TMAX; ++t) xv[t] = bld(rx, toff[t] >= 0x3FFFFFF0u ? SK_OOB : (xk + toff[t]) * 4u);
+        for (int t = 0; t < TMAX; ++t) xv[t] = buf_ld(rx, toff[t] >= 0x3FFFFFF0u ? SK_OOB : (xk + toff[t]) * 4u);
 #pragma unroll
         for (int t = 0; t < TMAX; ++t)
 #pragma unroll
@@ -124,7 +120,7 @@ __global__ __launch_bounds__(64 * NWV) void small_out_kernel(SkArgs a) {
       } else {
         for (int t = 0; t < T; ++t) {
           const unsigned o = tap_off(t / KW, t % KW);
-          const float xv = bld(rx, o >= 0x3FFFFFF0u ? SK_OOB : (xk + o) * 4u);
+          const float xv = buf_ld(rx, o >= 0x3FFFFFF0u ? SK_OOB : (xk + o) * 4u);
 #pragma unroll
           for (int m = 0; m < MS; ++m) acc[m] = fmaf(wk[t * MS + m], xv, acc[m]);
         }
@@ -199,7 +195,7 @@ __global__ __launch_bounds__(256) void small_in_kernel(SkArgs a) {
   const int b = q / HWo, r = q - b * HWo;
   const int oh = r / a.Wo, ow0 = r - oh * a.Wo;
   const int HWi = a.Hin * a.Win;
-  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, (short)0, a.x_range, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rx = buf_rsrc(a.x, a.x_range);
   const unsigned xb = (unsigned)((long)b * a.x_bs);
   float xv[KT][PX];
 #pragma unroll
@@ -212,7 +208,7 @@ __global__ __launch_bounds__(256) void small_in_kernel(SkArgs a) {
         if (!a.transposed) { ih = oh * a.stride - a.pad + kh; iw = ow * a.stride - a.pad + kw; }
         else { ih = oh + a.pad - kh; iw = ow + a.pad - kw; }
         const bool ok = ((unsigned)ih < (unsigned)a.Hin) & ((unsigned)iw < (unsigned)a.Win);
-        xv[j][p] = bld(rx, ok ? (xb + (unsigned)k * HWi + (unsigned)(ih * a.Win + iw)) * 4u : SK_OOB);
+        xv[j][p] = buf_ld(rx, ok ? (xb + (unsigned)k * HWi + (unsigned)(ih * a.Win + iw)) * 4u : SK_OOB);
       } else {
         xv[j][p] = 0.f;
       }
@@ -277,8 +273,8 @@ __global__ __launch_bounds__(256) void wgrad_small_kernel(WsArgs a) {
   const long total = (long)a.nb * HWo;
   const long p0 = (long)blockIdx.y * a.pix_per_block;
   const long p1 = min(total, p0 + a.pix_per_block);
-  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, (short)0, a.x_range, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc((void*)a.dy, (short)0, a.dy_range, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rx = buf_rsrc(a.x, a.x_range);
+  const __amdgpu_buffer_rsrc_t rg = buf_rsrc(a.dy, a.dy_range);
 
   float acc[S][T];
 #pragma unroll
@@ -312,23 +308,23 @@ __global__ __launch_bounds__(256) void wgrad_small_kernel(WsArgs a) {
       float g[S];
 #pragma unroll
       for (int s = 0; s < S; ++s)
-        g[s] = s < a.nsmall ? bld(rg, (gb + (unsigned)s * HWo) * 4u) : 0.f;
+        g[s] = s < a.nsmall ? buf_ld(rg, (gb + (unsigned)s * HWo) * 4u) : 0.f;
       const unsigned xc = xb + (unsigned)c * HWi;
 #pragma unroll
       for (int t = 0; t < T; ++t) {
-        const float xv = bld(rx, toff[t] >= 0x3FFFFFF0u ? SK_OOB : (xc + toff[t]) * 4u);
+        const float xv = buf_ld(rx, toff[t] >= 0x3FFFFFF0u ? SK_OOB : (xc + toff[t]) * 4u);
 #pragma unroll
         for (int s = 0; s < S; ++s) acc[s][t] = fmaf(g[s], xv, acc[s][t]);
       }
     } else {
-      const float g = bld(rg, (gb + (unsigned)c * HWo) * 4u);
+      const float g = buf_ld(rg, (gb + (unsigned)c * HWo) * 4u);
 #pragma unroll
       for (int s = 0; s < S; ++s) {
         if (s >= a.nsmall) break;
         const unsigned xc = xb + (unsigned)s * HWi;
 #pragma unroll
         for (int t = 0; t < T; ++t) {
-          const float xv = bld(rx, toff[t] >= 0x3FFFFFF0u ? SK_OOB : (xc + toff[t]) * 4u);
+          const float xv = buf_ld(rx, toff[t] >= 0x3FFFFFF0u ? SK_OOB : (xc + toff[t]) * 4u);
           acc[s][t] = fmaf(g, xv, acc[s][t]);
         }
       }
@@ -369,11 +365,8 @@ __global__ __launch_bounds__(256) void wgrad_small_pw4_kernel(WsArgs a) {
   const long total = (long)a.nb * HW;
   const long p0 = (long)blockIdx.y * a.pix_per_block;
   const long p1 = min(total, p0 + a.pix_per_block);
-  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, (short)0, a.x_range, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc((void*)a.dy, (short)0, a.dy_range, 0x00020000);
-  auto ld4 = [](__amdgpu_buffer_rsrc_t r, unsigned off) {
-    return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0));
-  };
+  const __amdgpu_buffer_rsrc_t rx = buf_rsrc(a.x, a.x_range);
+  const __amdgpu_buffer_rsrc_t rg = buf_rsrc(a.dy, a.dy_range);
   float acc[S];
 #pragma unroll
   for (int s = 0; s < S; ++s) acc[s] = 0.f;
@@ -391,15 +384,15 @@ __global__ __launch_bounds__(256) void wgrad_small_pw4_kernel(WsArgs a) {
       const unsigned xb = (unsigned)((long)b * a.x_bs) + r, gb = (unsigned)((long)b * a.dy_bs) + r;
       // (an out-of-range quad reads zeros through the buffer range check: offset SK_OOB)
       if (SMALL_OUT) {
-        one[u] = ld4(rx, ok ? (xb + (unsigned)c * HW) * 4u : SK_OOB);
+        one[u] = buf_ld4(rx, ok ? (xb + (unsigned)c * HW) * 4u : SK_OOB);
 #pragma unroll
         for (int s = 0; s < S; ++s)
-          many[u][s] = s < a.nsmall ? ld4(rg, ok ? (gb + (unsigned)s * HW) * 4u : SK_OOB) : float4{0.f, 0.f, 0.f, 0.f};
+          many[u][s] = s < a.nsmall ? buf_ld4(rg, ok ? (gb + (unsigned)s * HW) * 4u : SK_OOB) : float4{0.f, 0.f, 0.f, 0.f};
       } else {
-        one[u] = ld4(rg, ok ? (gb + (unsigned)c * HW) * 4u : SK_OOB);
+        one[u] = buf_ld4(rg, ok ? (gb + (unsigned)c * HW) * 4u : SK_OOB);
 #pragma unroll
         for (int s = 0; s < S; ++s)
-          many[u][s] = s < a.nsmall ? ld4(rx, ok ? (xb + (unsigned)s * HW) * 4u : SK_OOB) : float4{0.f, 0.f, 0.f, 0.f};
+          many[u][s] = s < a.nsmall ? buf_ld4(rx, ok ? (xb + (unsigned)s * HW) * 4u : SK_OOB) : float4{0.f, 0.f, 0.f, 0.f};
       }
       r += 1024;
       while (r >= HW) { r -= HW; ++b; }

@@ -77,11 +77,9 @@ __global__ __launch_bounds__(256, 2) void tconv_kernel(TcArgs g) {
   const int m0 = m_t * BM, q0 = nt_i * BN;
 
   const int HWin = g.Hin * g.Win;
-  const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)g.Wt, (short)0, (unsigned)((long)g.ntaps * g.M * g.K * (ABF ? 2 : 4)), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rw = buf_rsrc(g.Wt, (unsigned)((long)g.ntaps * g.M * g.K * (ABF ? 2 : 4)));
   constexpr int XB = XH ? 2 : 4;   // bytes per X element
-  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)((const char*)g.X + (long)bimg * g.x_bs * XB), (short)0, (unsigned)((long)g.K * HWin * XB), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rx = buf_rsrc((const char*)g.X + (long)bimg * g.x_bs * XB, (unsigned)((long)g.K * HWin * XB));
 
   // B staging: thread -> column c = tid % 128, channels 16*(tid/128) .. +15 of the step
   const int col = tid & 127, kc = wave >> 1;   // kc uniform per wave: channel rows are soffsets
@@ -224,10 +222,9 @@ __global__ __launch_bounds__(256, 2) void tconv_kernel(TcArgs g) {
   // ---- epilogue: dst pixel of this lane's column, channel rows via scalar offsets ----
   const int HWd = g.Hdst * g.Wdst;
   const unsigned range = (unsigned)((long)g.M * HWd * 4);
-  const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(g.Y + (long)bimg * g.y_bs), (short)0, range, 0x00020000);
+  const __amdgpu_buffer_rsrc_t ry = buf_rsrc(g.Y + (long)bimg * g.y_bs, range);
   __amdgpu_buffer_rsrc_t rg = ry;
-  if (g.gpre) rg = __builtin_amdgcn_make_buffer_rsrc((void*)(g.gpre + (long)bimg * g.gpre_bs), (short)0, range, 0x00020000);
+  if (g.gpre) rg = buf_rsrc(g.gpre + (long)bimg * g.gpre_bs, range);
   const bool full = m0 + BM <= g.M;
 #pragma unroll
   for (int j = 0; j < TN; ++j) {

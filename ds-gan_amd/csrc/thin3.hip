@@ -35,12 +35,6 @@ struct T3Args {
   unsigned x_range, g_range;
 };
 
-__device__ __forceinline__ float4 t3_ld4(__amdgpu_buffer_rsrc_t r, unsigned off) {
-  return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0));
-}
-__device__ __forceinline__ float t3_ld1(__amdgpu_buffer_rsrc_t r, unsigned off) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)off, 0, 0));
-}
 
 // Row h of plane `plane` (element offset), columns c0-1 .. c0+4 of this lane (c0 = seg*256 + 4*lane):
 // the loads (t3_row_ld: the lane's 16 bytes + the outer lanes' halo columns) and the assembly from
@@ -51,10 +45,10 @@ __device__ __forceinline__ T3Row t3_row_ld(__amdgpu_buffer_rsrc_t r, unsigned pl
   const bool ok = (unsigned)h < (unsigned)H;
   const unsigned rowoff = plane + (unsigned)(h * W);
   T3Row o;
-  o.q = t3_ld4(r, ok ? (rowoff + (unsigned)c0) * 4u : T3_OOB);
+  o.q = buf_ld4(r, ok ? (rowoff + (unsigned)c0) * 4u : T3_OOB);
   // halo columns of the segment's outer lanes (a neighbouring segment, or the zero padding)
-  o.el = t3_ld1(r, (ok && lane == 0 && c0 > 0) ? (rowoff + (unsigned)c0 - 1u) * 4u : T3_OOB);
-  o.er = t3_ld1(r, (ok && lane == 63 && c0 + 4 < W) ? (rowoff + (unsigned)c0 + 4u) * 4u : T3_OOB);
+  o.el = buf_ld(r, (ok && lane == 0 && c0 > 0) ? (rowoff + (unsigned)c0 - 1u) * 4u : T3_OOB);
+  o.er = buf_ld(r, (ok && lane == 63 && c0 + 4 < W) ? (rowoff + (unsigned)c0 + 4u) * 4u : T3_OOB);
   return o;
 }
 __device__ __forceinline__ void t3_row_asm(const T3Row& o, int lane, float (&v)[6]) {
@@ -83,7 +77,7 @@ __global__ __launch_bounds__(256) void thin3_fwd_kernel(T3Args a) {
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   int b, h0, c0;
   t3_strip(blockIdx.x, a.H, a.W, b, h0, c0, lane);
-  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, (short)0, a.x_range, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rx = buf_rsrc(a.x, a.x_range);
   const unsigned HW = (unsigned)(a.H * a.W);
   float acc[4][4][MS];
   // the next channel's 6 rows are loaded before this channel's FMAs (one channel in flight)
@@ -176,8 +170,8 @@ __global__ __launch_bounds__(256) void thin3_wgrad_kernel(T3Args a) {
   const int kb = (blockIdx.x * 4 + wave) * CW;
   const int nstrips = a.nb * (a.H >> 2) * (a.W >> 8);
   const int s0 = blockIdx.y * a.strips_per_wg, s1 = min(nstrips, s0 + a.strips_per_wg);
-  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, (short)0, a.x_range, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc((void*)a.g, (short)0, a.g_range, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rx = buf_rsrc(a.x, a.x_range);
+  const __amdgpu_buffer_rsrc_t rg = buf_rsrc(a.g, a.g_range);
   const unsigned HW = (unsigned)(a.H * a.W);
   float acc[CW][MS][9];
 #pragma unroll
@@ -195,7 +189,7 @@ __global__ __launch_bounds__(256) void thin3_wgrad_kernel(T3Args a) {
     for (int m = 0; m < MS; ++m)
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        gv[m][r] = t3_ld4(rg, ((unsigned)((long)b * a.g_bs) + (unsigned)m * HW + (unsigned)((h0 + r) * a.W + c0)) * 4u);
+        gv[m][r] = buf_ld4(rg, ((unsigned)((long)b * a.g_bs) + (unsigned)m * HW + (unsigned)((h0 + r) * a.W + c0)) * 4u);
 #pragma unroll
     for (int c = 0; c < CW; ++c) {
       const int k = kb + c;
@@ -236,7 +230,7 @@ __global__ __launch_bounds__(256) void thin3_dgrad_kernel(T3Args a) {
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   int b, h0, c0;
   t3_strip(blockIdx.x, a.H, a.W, b, h0, c0, lane);
-  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, (short)0, a.x_range, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rx = buf_rsrc(a.x, a.x_range);
   const unsigned HW = (unsigned)(a.H * a.W);
   float in[MS][6][6];
 #pragma unroll

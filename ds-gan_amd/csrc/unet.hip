@@ -171,13 +171,6 @@ __global__ __launch_bounds__(256) void tanh_bwd_kernel(const float* __restrict__
   }
 }
 
-static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-static inline unsigned ew_grid_u(long n) {
-  long g = (n + 255) / 256;
-  if (g > 16384) g = 16384;
-  if (g < 1) g = 1;
-  return (unsigned)g;
-}
 }  // namespace dsg
 
 using namespace dsg;
@@ -275,14 +268,14 @@ int dsgan_dropout_apply(const float* x, long x_bs, float* y, long y_bs, int N, l
 
 int dsgan_tanh_fwd(const float* x, long n, float* y, hipStream_t st) {
   DSG_REQUIRE(x && y && n > 0, "dsgan_tanh_fwd: bad args");
-  hipLaunchKernelGGL(tanh_fwd_kernel, dim3(ew_grid_u(n)), dim3(256), 0, st, x, n, y);
+  hipLaunchKernelGGL(tanh_fwd_kernel, dim3(ew_grid(n)), dim3(256), 0, st, x, n, y);
   DSG_CHECK_LAUNCH();
   return 0;
 }
 // dx (+)= dy * (1 - y^2) from the saved OUTPUT
 int dsgan_tanh_bwd(const float* y, const float* dy, long n, float* dx, int accumulate, hipStream_t st) {
   DSG_REQUIRE(y && dy && dx && n > 0, "dsgan_tanh_bwd: bad args");
-  hipLaunchKernelGGL(tanh_bwd_kernel, dim3(ew_grid_u(n)), dim3(256), 0, st, y, dy, n, dx, accumulate);
+  hipLaunchKernelGGL(tanh_bwd_kernel, dim3(ew_grid(n)), dim3(256), 0, st, y, dy, n, dx, accumulate);
   DSG_CHECK_LAUNCH();
   return 0;
 }

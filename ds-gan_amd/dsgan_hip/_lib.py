@@ -123,7 +123,7 @@ SIGNATURES = {
     "dsgan_dwconv_multi_fwd": [P, L, P, P, P, P, P, P, P, P, P, L, I, I, I, I, I, I, S],
     "dsgan_dwconv_multi_wgrad_workspace": [I, I, I, I],
     "dsgan_dwconv_multi_wgrad": [P, L, P, L, P, P, P, P, P, P, P, P, I, I, I, I, P, L, S],
-    # norm_pointwise.hip
+    # instnorm.hip
     "dsgan_instnorm_fwd": [P, L, P, P, L, P, L, P, P, I, I, I, I, F, F, S],
     "dsgan_instnorm_fwd_bf16": [P, L, P, L, P, P, I, I, I, F, S],
     "dsgan_instnorm_bwd": [P, L, P, L, P, P, L, P, P, P, L, P, L, P, I, I, I, I, F, F, S],
@@ -131,15 +131,18 @@ SIGNATURES = {
     "dsgan_instnorm_workspace": [I, I, I],
     "dsgan_instnorm_fwd_ws": [P, L, P, P, L, P, L, P, P, I, I, I, I, F, F, P, L, S],
     "dsgan_instnorm_bwd_ws": [P, L, P, L, P, P, L, P, P, P, L, P, L, P, I, I, I, I, F, F, P, L, S],
+    # maxpool.hip
     "dsgan_maxpool_fwd": [P, L, P, L, P, I, I, I, I, I, S],
     "dsgan_maxpool_bwd": [P, L, P, P, L, I, I, I, I, I, I, S],
     "dsgan_maxpool_pyr_supported": [I, I, I],
     "dsgan_maxpool_pyr_fwd": [P, L, I] + [P] * 8 + [I, I, I, I, S],
     "dsgan_maxpool_pyr_bwd": [P, L, P] * 4 + [P, L] + [I] * 6 + [S],
+    # ca.hip
     "dsgan_plane_stats": [P, L, P, P, P, I, I, I, S],
     "dsgan_plane_stats_bwd": [P, P, P, P, L, I, I, I, S],
     "dsgan_ca_fwd": [P, P, P, P, P, P, P, I, I, I, S],
     "dsgan_ca_bwd": [P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, P, L, S],
+    # pointwise.hip
     "dsgan_add_n": [P, P, I, P, L, I, L, S],
     "dsgan_copy_strided": [P, L, P, L, I, L, S],
     "dsgan_copy_multi": [P, P, I, L, S],

@@ -434,7 +434,7 @@ int dsgan_dwconv_wgrad(const float* dy, long dy_bs, const float* x, long x_bs, f
                        hipStream_t stream);
 
 /* ---- InstanceNorm2d(affine=False, eps) fused with per-plane scale, residual and activation
- * (norm_pointwise.hip): nn.InstanceNorm2d at MixConvNeXtML.py:54,80,113-116,151,158,221,
+ * (instnorm.hip): nn.InstanceNorm2d at MixConvNeXtML.py:54,80,113-116,151,158,221,
  * 335-420 and networks.py:556,565.  y = act(IN(scale*x) + res). */
 int dsgan_instnorm_fwd(const float* x, long x_bs, const float* scale, const float* res,
                        long res_bs, float* y, long y_bs, float* mean, float* rstd, int N, int C,

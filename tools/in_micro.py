@@ -1,4 +1,4 @@
-"""Time the InstanceNorm kernels (norm_pointwise.hip) at the step's large-plane shapes: forward (fp32
+"""Time the InstanceNorm kernels (instnorm.hip) at the step's large-plane shapes: forward (fp32
 and bf16 output), backward (fp32 dx) and the 16-bit-dx backward of the ConvT nodes.  Each line ends
 in a hash of the outputs, so two builds can be compared bit for bit.
 
