@@ -37,19 +37,27 @@ __device__ __forceinline__ void adam_elem(float& p, float gr, float& m, float& v
   p = p - a.step_size * (mm / denom);
 }
 
+// The generator's moving average (--ema_decay) of the parameter adam_elem just produced:
+// ema.lerp_(p, w) with w = 1 - decay, in the at::lerp form adam_elem uses for m.
+__device__ __forceinline__ void ema_elem(float& e, float p, float w) {
+  e = w < 0.5f ? e + w * (p - e) : p - (p - e) * (1.f - w);
+}
+
 // VEC: p, g, m, v 16-byte aligned -- each lane moves float4s, the n % 4 tail elements go to the
 // first threads.  Otherwise one element per lane.
 // AMP: g is scaled by st[3] (1 / loss scale), the step count is st[4] (the scalars are formed here
 // from the doubles, as on the host for the plain form), and the whole update is skipped when
 // st[1] != 0.
-template <bool VEC, bool AMP>
+// EMA: the same lane also moves ema toward the new p by the weight we (8 more bytes per element
+// on the 28 the update streams); a skipped AMP step leaves ema untouched too.
+template <bool VEC, bool AMP, bool EMA>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v, long n, AdamScal a,
                                                    double lr, double b1, double b2, double eps,
-                                                   const float* __restrict__ st) {
+                                                   const float* __restrict__ st, float* __restrict__ ema, float we) {
   float inv = 1.f;
   if constexpr (AMP) {
-    if (st[1] != 0.f) return;   // overflowed step: parameters and moments untouched
+    if (st[1] != 0.f) return;   // overflowed step: parameters, moments and the average untouched
     inv = st[3];
     const double t = (double)st[4];
     a.w1 = (float)(1.0 - b1);
@@ -75,37 +83,67 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
       reinterpret_cast<float4*>(m)[i] = mm;
       reinterpret_cast<float4*>(v)[i] = vv;
       reinterpret_cast<float4*>(p)[i] = pp;
+      if constexpr (EMA) {
+        float4 ee = reinterpret_cast<const float4*>(ema)[i];
+        ema_elem(ee.x, pp.x, we);
+        ema_elem(ee.y, pp.y, we);
+        ema_elem(ee.z, pp.z, we);
+        ema_elem(ee.w, pp.w, we);
+        reinterpret_cast<float4*>(ema)[i] = ee;
+      }
     }
     const long e = (n4 << 2) + tid;
     if (e < n) {
       float gr = g[e];
       if constexpr (AMP) gr *= inv;
       adam_elem(p[e], gr, m[e], v[e], a);
+      if constexpr (EMA) ema_elem(ema[e], p[e], we);
     }
   } else {
     for (long e = tid; e < n; e += stride) {
       float gr = g[e];
       if constexpr (AMP) gr *= inv;
       adam_elem(p[e], gr, m[e], v[e], a);
+      if constexpr (EMA) ema_elem(ema[e], p[e], we);
     }
   }
 }
 
-static bool adam_vec_ok(const float* p, const float* g, const float* m, const float* v) {
-  return (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0;
+// (ema: nullptr in the plain forms, which is 16-byte aligned)
+static bool adam_vec_ok(const float* p, const float* g, const float* m, const float* v, const float* ema) {
+  return (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) & 15) == 0;
 }
 
-template <bool AMP>
+template <bool AMP, bool EMA>
 static void adam_launch(float* p, const float* g, float* m, float* v, long n, const AdamScal& a, double lr, double b1,
-                        double b2, double eps, const float* state, hipStream_t st) {
+                        double b2, double eps, const float* state, float* ema, float we, hipStream_t st) {
   long blocks = (n + 1023) / 1024;
   if (blocks > 8192) blocks = 8192;
-  if (adam_vec_ok(p, g, m, v))
-    hipLaunchKernelGGL((adam_kernel<true, AMP>), dim3((unsigned)blocks), dim3(256), 0, st, p, g, m, v, n, a, lr, b1,
-                       b2, eps, state);
+  if (adam_vec_ok(p, g, m, v, ema))
+    hipLaunchKernelGGL((adam_kernel<true, AMP, EMA>), dim3((unsigned)blocks), dim3(256), 0, st, p, g, m, v, n, a, lr,
+                       b1, b2, eps, state, ema, we);
   else
-    hipLaunchKernelGGL((adam_kernel<false, AMP>), dim3((unsigned)blocks), dim3(256), 0, st, p, g, m, v, n, a, lr, b1,
-                       b2, eps, state);
+    hipLaunchKernelGGL((adam_kernel<false, AMP, EMA>), dim3((unsigned)blocks), dim3(256), 0, st, p, g, m, v, n, a, lr,
+                       b1, b2, eps, state, ema, we);
+}
+
+// a <-> b in place: each lane holds both values before it stores either, so no temporary buffer
+template <bool VEC>
+__global__ __launch_bounds__(256) void swap_kernel(float* __restrict__ a, float* __restrict__ b, long n) {
+  const long tid = blockIdx.x * 256L + threadIdx.x, stride = (long)gridDim.x * 256;
+  if constexpr (VEC) {
+    const long n4 = n >> 2;
+    for (long i = tid; i < n4; i += stride) {
+      const float4 x = reinterpret_cast<const float4*>(a)[i];
+      const float4 y = reinterpret_cast<const float4*>(b)[i];
+      reinterpret_cast<float4*>(a)[i] = y;
+      reinterpret_cast<float4*>(b)[i] = x;
+    }
+    const long e = (n4 << 2) + tid;
+    if (e < n) { const float x = a[e]; a[e] = b[e]; b[e] = x; }
+  } else {
+    for (long e = tid; e < n; e += stride) { const float x = a[e]; a[e] = b[e]; b[e] = x; }
+  }
 }
 }  // namespace dsg
 
@@ -114,7 +152,36 @@ extern "C" int dsgan_adam(float* p, const float* g, float* m, float* v, long n, 
                           double beta2, double eps, int step, hipStream_t st) {
   DSG_REQUIRE(p && g && m && v && n >= 0 && step >= 1, "dsgan_adam: bad args");
   if (n == 0) return 0;
-  adam_launch<false>(p, g, m, v, n, adam_scal(lr, beta1, beta2, eps, step), lr, beta1, beta2, eps, nullptr, st);
+  adam_launch<false, false>(p, g, m, v, n, adam_scal(lr, beta1, beta2, eps, step), lr, beta1, beta2, eps, nullptr,
+                            nullptr, 0.f, st);
+  DSG_CHECK_LAUNCH();
+  return 0;
+}
+
+// dsgan_adam, and ema.lerp_(p, 1 - ema_decay) on the updated p in the same pass
+extern "C" int dsgan_adam_ema(float* p, const float* g, float* m, float* v, float* ema, long n, double lr,
+                              double beta1, double beta2, double eps, double ema_decay, int step, hipStream_t st) {
+  DSG_REQUIRE(p && g && m && v && n >= 0 && step >= 1, "dsgan_adam_ema: bad args");
+  DSG_REQUIRE(ema != nullptr, "dsgan_adam_ema: ema is null");
+  DSG_REQUIRE(ema_decay >= 0.0 && ema_decay < 1.0, "dsgan_adam_ema: ema_decay %g outside [0, 1)", ema_decay);
+  if (n == 0) return 0;
+  adam_launch<false, true>(p, g, m, v, n, adam_scal(lr, beta1, beta2, eps, step), lr, beta1, beta2, eps, nullptr, ema,
+                           (float)(1.0 - ema_decay), st);
+  DSG_CHECK_LAUNCH();
+  return 0;
+}
+
+// a <-> b (n floats each, not overlapping), one launch, no temporary: Pix2PixModel.ema_scope
+extern "C" int dsgan_swap(float* a, float* b, long n, hipStream_t st) {
+  DSG_REQUIRE(a && b && n >= 0, "dsgan_swap: bad args");
+  DSG_REQUIRE(a + n <= b || b + n <= a, "dsgan_swap: the buffers overlap");
+  if (n == 0) return 0;
+  long blocks = (n + 1023) / 1024;
+  if (blocks > 8192) blocks = 8192;
+  if ((((uintptr_t)a | (uintptr_t)b) & 15) == 0)
+    hipLaunchKernelGGL((swap_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, st, a, b, n);
+  else
+    hipLaunchKernelGGL((swap_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, st, a, b, n);
   DSG_CHECK_LAUNCH();
   return 0;
 }
@@ -189,7 +256,18 @@ int dsgan_adam_amp(float* p, const float* g, float* m, float* v, long n, double 
                    double eps, const float* state, hipStream_t st) {
   DSG_REQUIRE(p && g && m && v && state && n >= 0, "dsgan_adam_amp: bad args");
   if (n == 0) return 0;
-  adam_launch<true>(p, g, m, v, n, AdamScal{}, lr, beta1, beta2, eps, state, st);
+  adam_launch<true, false>(p, g, m, v, n, AdamScal{}, lr, beta1, beta2, eps, state, nullptr, 0.f, st);
+  DSG_CHECK_LAUNCH();
+  return 0;
+}
+// dsgan_adam_amp, and ema.lerp_(p, 1 - ema_decay) on the updated p; a skipped step does not average
+int dsgan_adam_amp_ema(float* p, const float* g, float* m, float* v, float* ema, long n, double lr, double beta1,
+                       double beta2, double eps, double ema_decay, const float* state, hipStream_t st) {
+  DSG_REQUIRE(p && g && m && v && state && n >= 0, "dsgan_adam_amp_ema: bad args");
+  DSG_REQUIRE(ema != nullptr, "dsgan_adam_amp_ema: ema is null");
+  DSG_REQUIRE(ema_decay >= 0.0 && ema_decay < 1.0, "dsgan_adam_amp_ema: ema_decay %g outside [0, 1)", ema_decay);
+  if (n == 0) return 0;
+  adam_launch<true, true>(p, g, m, v, n, AdamScal{}, lr, beta1, beta2, eps, state, ema, (float)(1.0 - ema_decay), st);
   DSG_CHECK_LAUNCH();
   return 0;
 }

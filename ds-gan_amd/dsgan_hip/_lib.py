@@ -214,6 +214,9 @@ SIGNATURES = {
     "dsgan_cb16_tap_bwd": [P, P, P, P, P, I, I, I, I, P, S],
     # adam.hip
     "dsgan_adam": [P, P, P, P, L, D, D, D, D, I, S],
+    "dsgan_adam_ema": [P, P, P, P, P, L, D, D, D, D, D, I, S],
+    "dsgan_adam_amp_ema": [P, P, P, P, P, L, D, D, D, D, D, P, S],
+    "dsgan_swap": [P, P, L, S],
 }
 
 _lib = None

@@ -14,7 +14,8 @@ divided by it again.  Unlike GradScaler nothing here syncs with the host:
     is marked skipped and the scale halves; after ``growth_interval`` clean steps it doubles;
   * ``FlatAdam.step`` then runs dsgan_adam_amp, which divides by the step's scale and does
     nothing on a skipped step (its bias-correction step count, ``state[4]``, is not advanced --
-    GradScaler skips optimizer.step()).
+    GradScaler skips optimizer.step()); with ``--ema_decay`` it is dsgan_adam_amp_ema, which on a
+    skipped step leaves the generator's moving average untouched as well.
 One scaler per network (D and G have their own backward and optimizer).  Defaults are
 GradScaler's (init 2^16, growth 2, backoff 0.5, interval 2000).
 

@@ -62,15 +62,41 @@ class FlatAdam(torch.optim.Optimizer):
 
     Subclasses torch.optim.Optimizer so the reference's LambdaLR scheduler (get_scheduler,
     DSGAN/models/networks.py:33-46) drives ``param_groups[0]['lr']`` exactly as before.
+
+    ``ema_decay`` > 0 (--ema_decay): ``self.ema`` is a second flat buffer, a copy of ``flat.data`` at
+    construction, and the step's one kernel also moves it toward the updated parameters,
+    ``ema.lerp_(p, 1 - ema_decay)`` (dsgan_adam_ema / dsgan_adam_amp_ema): decided on the device, so a
+    step the scaler skips does not average and a graph replay averages.  0: no buffer, the plain
+    entry points.
     """
 
-    def __init__(self, flat, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, scaler=None):
+    def __init__(self, flat, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, scaler=None, ema_decay=0.0):
         super().__init__(flat.params, dict(lr=lr, betas=betas, eps=eps))
         self.flat = flat
         self.scaler = scaler   # dsgan_hip.amp.LossScaler (--precision fp16): unscale / skip on device
         self.m = torch.zeros_like(flat.data)
         self.v = torch.zeros_like(flat.data)
         self.step_count = 0
+        self.ema_decay = float(ema_decay)
+        if not 0.0 <= self.ema_decay < 1.0:
+            raise ValueError("ema_decay must lie in [0, 1), got %r" % (ema_decay,))
+        self.ema = flat.data.clone() if self.ema_decay > 0.0 else None
+
+    def reset_ema(self):
+        """The average restarts from the current parameters (after a checkpoint without an EMA file)."""
+        if self.ema is not None:
+            with torch.no_grad():
+                self.ema.copy_(self.flat.data)
+
+    def ema_views(self, module=None):
+        """(parameter, its view into the EMA buffer) by the layout offsets: of ``module``'s parameters,
+        or of every parameter of the buffer."""
+        if self.ema is None:
+            raise RuntimeError("FlatAdam.ema_views: no EMA buffer (ema_decay is 0)")
+        offs = {id(p): (off, k) for p, off, k in self.flat.layout}
+        for p in (module.parameters() if module is not None else self.flat.params):
+            off, k = offs[id(p)]
+            yield p, self.ema[off:off + k].view(p.shape)
 
     def zero_grad(self, set_to_none=False):
         self.flat.zero_grad()
@@ -80,7 +106,16 @@ class FlatAdam(torch.optim.Optimizer):
         self.step_count += 1
         g = self.param_groups[0]
         b1, b2 = g["betas"]
-        if self.scaler is not None:
+        if self.ema is not None:   # the same update, and the moving average in the same pass
+            if self.scaler is not None:
+                call("dsgan_adam_amp_ema", ptr(self.flat.data), ptr(self.flat.grad), ptr(self.m), ptr(self.v),
+                     ptr(self.ema), self.flat.numel, float(g["lr"]), float(b1), float(b2), float(g["eps"]),
+                     self.ema_decay, ptr(self.scaler.state), stream())
+            else:
+                call("dsgan_adam_ema", ptr(self.flat.data), ptr(self.flat.grad), ptr(self.m), ptr(self.v),
+                     ptr(self.ema), self.flat.numel, float(g["lr"]), float(b1), float(b2), float(g["eps"]),
+                     self.ema_decay, self.step_count, stream())
+        elif self.scaler is not None:
             # the scaler's check() has run on this gradient: g / scale, skipped on overflow, its
             # own step count for the bias corrections (step_count here counts calls)
             call("dsgan_adam_amp", ptr(self.flat.data), ptr(self.flat.grad), ptr(self.m), ptr(self.v),

@@ -13,7 +13,10 @@ image and a last ``mean`` row.  Everything lands in ``<results_dir>/<name>/<phas
 relative --results_dir is taken under --out.  ``--how_many`` images are evaluated, exactly.
 
 ``--model test --dataset_mode single`` has no labels: ``[input | result]`` panels and no CSV.
-``--no_images`` skips the PNGs.  Evaluation is single-process (WORLD_SIZE > 1 is refused), batches are
+``--no_images`` skips the PNGs.  ``--use_ema`` scores the averaged generator a run with ``--ema_decay``
+saved: it loads ``<which_epoch>_net_G_ema.pth`` (or ``<which_epoch>_useSE_net_G_ema.pth``) instead of the
+raw generator's file and writes to ``<phase>_<which_epoch>_ema/``, beside the raw results; without such a
+file it fails, naming the paths it tried.  Evaluation is single-process (WORLD_SIZE > 1 is refused), batches are
 taken in order and never flipped, and ``--aspect_ratio`` other than 1.0 (the reference visualiser's
 resize) is refused.  The seed is 20, as in train.py.
 """
@@ -31,10 +34,22 @@ if HERE not in sys.path:
 import torch  # noqa: E402
 
 
-def results_dir(opt, out):
-    """<results_dir>/<name>/<phase>_<which_epoch>; a relative --results_dir is taken under ``out``."""
+def results_dir(opt, out, use_ema=False):
+    """<results_dir>/<name>/<phase>_<which_epoch>, with ``_ema`` appended for the averaged generator; a
+    relative --results_dir is taken under ``out``."""
     root = opt.results_dir if os.path.isabs(opt.results_dir) else os.path.join(out, opt.results_dir)
-    return os.path.join(root, opt.name, "%s_%s" % (opt.phase.strip("/\\").replace("/", "_"), opt.which_epoch))
+    leaf = "%s_%s" % (opt.phase.strip("/\\").replace("/", "_"), opt.which_epoch)
+    return os.path.join(root, opt.name, leaf + ("_ema" if use_ema else ""))
+
+
+def ema_checkpoint(save_dir, which_epoch):
+    """The averaged generator's checkpoint for ``which_epoch`` in ``save_dir`` (either name form)."""
+    paths = [os.path.join(save_dir, n % which_epoch) for n in ("%s_net_G_ema.pth", "%s_useSE_net_G_ema.pth")]
+    for p in paths:
+        if os.path.exists(p):
+            return p
+    raise FileNotFoundError("--use_ema: no EMA generator checkpoint (train with --ema_decay): tried %s"
+                            % " and ".join(paths))
 
 
 def check_options(opt):
@@ -117,17 +132,23 @@ def main(argv=None):
     ap.add_argument("--out", default=os.path.abspath(os.path.join("..", "resext50_vision1")))
     ap.add_argument("--dataroot", default="/root/dataset/256x256")
     ap.add_argument("--no_images", action="store_true", help="score only: write no PNG panels")
+    ap.add_argument("--use_ema", action="store_true",
+                    help="score the averaged generator (<which_epoch>_net_G_ema.pth) into <phase>_<which_epoch>_ema/")
     known, rest = ap.parse_known_args(argv)
     setup_seed(20)
     opt = TestOptions().parse(known.dataroot, known.out, rest)
     check_options(opt)
     opt = eval_options(opt)
-    dest = results_dir(opt, known.out)
+    if known.use_ema:   # before anything is written
+        ema_checkpoint(os.path.join(opt.checkpoints_dir, opt.name), opt.which_epoch)
+    dest = results_dir(opt, known.out, known.use_ema)
     os.makedirs(dest, exist_ok=True)
     dataset = CreateDataLoader(opt, "test", local=True).load_data()
     how_many = min(int(opt.how_many), len(dataset))
     print("#test images = %d" % how_many)
     model = create_model(opt)
+    if known.use_ema:   # load_networks then reads the _ema files (same name forms, same key handling)
+        model.load_suffix = "_ema"
     model.setup(opt)
     model.eval()
     metrics = EvalMetrics(model.device, max(how_many, 1))

@@ -32,6 +32,9 @@ class BaseModel:
         self.visual_names = []
         self.image_paths = []
 
+    ema_on = False     # a model that keeps a moving average of its generator (--ema_decay) says so
+    load_suffix = ""   # "_ema": load_networks reads the averaged generator's files (evaluate.py --use_ema)
+
     def set_input(self, input):
         self.input = input
 
@@ -43,6 +46,8 @@ class BaseModel:
             self.schedulers = [networks.get_scheduler(optimizer, opt) for optimizer in self.optimizers]
         if not self.isTrain or opt.continue_train:
             self.load_networks(opt.which_epoch)
+            if self.isTrain and self.ema_on:   # after G: a missing EMA file restarts it from the loaded weights
+                self.load_ema(opt.which_epoch)
         self.print_networks(opt.verbose)
 
     def eval(self):
@@ -83,7 +88,8 @@ class BaseModel:
 
     def save_networks(self, which_epoch):
         """'{epoch}_useSE_net_{G,D}.pth' as the reference writes (:95).  Keys carry no
-        ``module.`` prefix (no DataParallel wrapper); load_networks accepts both."""
+        ``module.`` prefix (no DataParallel wrapper); load_networks accepts both.  With --ema_decay
+        on, '{epoch}_useSE_net_G_ema.pth' as well: the averaged generator, G's keys and shapes."""
         os.makedirs(self.save_dir, exist_ok=True)
         for name in self.model_names:
             if isinstance(name, str):
@@ -91,17 +97,23 @@ class BaseModel:
                 net = getattr(self, "net" + name)
                 sd = OrderedDict((k, v.detach().cpu().clone()) for k, v in net.state_dict().items())
                 torch.save(sd, os.path.join(self.save_dir, save_filename))
+        if self.ema_on:
+            with self.ema_scope():
+                sd = OrderedDict((k, v.detach().cpu().clone()) for k, v in self.netG.state_dict().items())
+            torch.save(sd, os.path.join(self.save_dir, "%s_useSE_net_G_ema.pth" % which_epoch))
 
     def load_networks(self, which_epoch):
         """Reads '{epoch}_net_{name}.pth' like the reference (:119) and, if that is absent, the
         '{epoch}_useSE_net_{name}.pth' this build (and the reference) saves -- the reference's
-        save/load name mismatch is bridged instead of failing.  ``module.`` prefixes from
+        save/load name mismatch is bridged instead of failing.  (``load_suffix`` "_ema": the same two
+        names with ``_ema`` before the extension.)  ``module.`` prefixes from
         DataParallel checkpoints are stripped.  As the reference's ``load_state_dict(strict=False)``
         (:148): missing / unexpected keys are allowed (and printed), a shape mismatch raises."""
         for name in self.model_names:
             if isinstance(name, str):
                 net = getattr(self, "net" + name)
-                cands = ["%s_net_%s.pth" % (which_epoch, name), "%s_useSE_net_%s.pth" % (which_epoch, name)]
+                cands = ["%s_net_%s%s.pth" % (which_epoch, name, self.load_suffix),
+                         "%s_useSE_net_%s%s.pth" % (which_epoch, name, self.load_suffix)]
                 paths = [os.path.join(self.save_dir, c) for c in cands]
                 path = next((p for p in paths if os.path.exists(p)), paths[0])
                 print("loading the model from %s" % path)

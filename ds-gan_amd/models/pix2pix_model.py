@@ -36,7 +36,14 @@ Deliberate, documented deviations:
     DSGAN_D_BATCH say: the stacked batch-2N pass would mix the two batches' statistics.  A step
     that the fp16 loss scaler or the non-finite guard skips has still updated the running buffers
     (the forward ran), as under torch's GradScaler.
+  * --ema_decay d (0: off): an exponential moving average of the generator's parameters,
+    ``ema = d * ema + (1 - d) * weights`` after every applied generator step, kept in one flat buffer
+    on optimizer_G and updated by the Adam kernel itself (dsgan_hip.flat.FlatAdam): a skipped step
+    does not average, a graph replay does, and every rank computes the same average without any
+    exchange.  ``ema_scope()`` makes ``netG`` the averaged generator for a while; save_networks
+    writes it as ``{epoch}_useSE_net_G_ema.pth``.  BatchNorm running buffers are not averaged.
 """
+import contextlib
 import os
 import random
 
@@ -92,6 +99,9 @@ class Pix2PixModel(BaseModel):
 
     def initialize(self, opt):
         BaseModel.initialize(self, opt)
+        self.ema_decay = float(getattr(opt, "ema_decay", 0.0) or 0.0) if opt.isTrain else 0.0
+        if not 0.0 <= self.ema_decay < 1.0:
+            raise ValueError("--ema_decay must lie in [0, 1), got %r" % (opt.ema_decay,))
         if self.device.type != "cuda":
             raise RuntimeError("Pix2PixModel (MI355X build) needs a ROCm GPU: set --gpu_ids; "
                                "there is no CPU execution path")
@@ -144,7 +154,9 @@ class Pix2PixModel(BaseModel):
                 self.scaler_G, self.scaler_D = LossScaler.guard(self.device), LossScaler.guard(self.device)
             else:
                 self.scaler_G = self.scaler_D = None
-            self.optimizer_G = FlatAdam(self.flatG, lr=opt.lr, betas=(opt.beta1, 0.999), scaler=self.scaler_G)
+            # (the EMA buffer lives on the optimizer: one for the run, whatever graph pairs get captured)
+            self.optimizer_G = FlatAdam(self.flatG, lr=opt.lr, betas=(opt.beta1, 0.999), scaler=self.scaler_G,
+                                        ema_decay=self.ema_decay)
             self.optimizer_D = FlatAdam(self.flatD, lr=opt.lr, betas=(opt.beta1, 0.999), scaler=self.scaler_D)
             self.optimizers.append(self.optimizer_G)
             self.optimizers.append(self.optimizer_D)
@@ -479,6 +491,59 @@ class Pix2PixModel(BaseModel):
         if self.scaler_G is not None:
             self.scaler_G.check(self.flatG.grad)
         self.optimizer_G.step()
+
+    # ---- the averaged generator (--ema_decay) ----
+    @property
+    def ema_on(self):
+        return self.isTrain and self.ema_decay > 0.0
+
+    def _swap_ema(self):
+        _lib.call("dsgan_swap", _lib.ptr(self.flatG.data), _lib.ptr(self.optimizer_G.ema), self.flatG.numel,
+                  _lib.stream())
+        HF.bump_weight_generation(self.flatG.params)   # the cached tap-major / 16-bit weight copies
+
+    @contextlib.contextmanager
+    def ema_scope(self):
+        """Inside the scope ``netG`` is the EMA generator: the contents of flatG.data and the EMA buffer
+        are exchanged in place (dsgan_swap; every parameter stays the same view) and exchanged back on
+        exit, each time invalidating the cached weight copies.  BatchNorm running buffers are the live
+        ones.  Nothing else moves, so training afterwards is bit-identical to a run that never entered
+        the scope, replayed graphs included.  No optimizer step may run inside."""
+        if not self.ema_on:
+            raise RuntimeError("ema_scope: the generator keeps no moving average (--ema_decay is 0)")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("ema_scope: a HIP graph capture is in progress")
+        self._swap_ema()
+        try:
+            yield self.netG
+        finally:
+            self._swap_ema()
+
+    def load_ema(self, which_epoch):
+        """--continue_train: the EMA buffer from '{epoch}_net_G_ema.pth', else '{epoch}_useSE_net_G_ema.pth'
+        (parameters only; ``module.`` prefixes stripped); with neither, the average restarts from the
+        generator's loaded weights."""
+        cands = ["%s_net_G_ema.pth" % which_epoch, "%s_useSE_net_G_ema.pth" % which_epoch]
+        path = next((p for p in (os.path.join(self.save_dir, c) for c in cands) if os.path.exists(p)), None)
+        if path is None:
+            print("no EMA checkpoint for epoch %s in %s: the average starts from the loaded generator"
+                  % (which_epoch, self.save_dir))
+            self.optimizer_G.reset_ema()
+            return
+        print("loading the EMA generator from %s" % path)
+        sd = torch.load(path, map_location="cpu", weights_only=True)
+        sd = {(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()}
+        views = {id(p): e for p, e in self.optimizer_G.ema_views()}
+        named = list(self.netG.named_parameters())
+        missing = [k for k, _ in named if k not in sd]
+        if missing:
+            raise RuntimeError("EMA checkpoint %s lacks the generator parameters %s" % (path, missing))
+        with torch.no_grad():
+            for k, p in named:
+                if tuple(sd[k].shape) != tuple(p.shape):
+                    raise RuntimeError("EMA checkpoint %s: size mismatch for %s: %s vs model %s"
+                                       % (path, k, tuple(sd[k].shape), tuple(p.shape)))
+                views[id(p)].copy_(sd[k].to(self.device, torch.float32))
 
     # ---- train.py helpers (DSGAN/models/pix2pix_model.py:292-310) ----
     def get_img_tir(self, input):

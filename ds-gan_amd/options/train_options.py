@@ -38,6 +38,11 @@ class TrainOptions(BaseOptions):
                                  "query (-1: on for one process with device-side loss scaling / guard)")
         parser.add_argument("--nonfinite_guard", type=int, default=-1, choices=[-1, 0, 1],
                             help="skip an optimizer step whose gradient has inf/nan (-1: on for bf16)")
+        # build extension: an exponential moving average of the generator's weights, updated by the
+        # generator's Adam kernel on every applied step (ema = decay * ema + (1 - decay) * weights);
+        # saved as {epoch}_useSE_net_G_ema.pth beside the raw G, scored by evaluate.py --use_ema
+        parser.add_argument("--ema_decay", type=float, default=0.0,
+                            help="decay of the generator's weight average, in [0, 1) (0: off; e.g. 0.999)")
         self.isTrain = True
         return parser
 

@@ -20,7 +20,9 @@ checkpoints and CSV files, behind a barrier.
 ``--eval_freq N`` (default 0: off) with ``--eval_phase`` (default ``test_all/``): every N epochs rank 0
 scores the generator in eval mode on that split (evaluate.py's pass) and appends
 ``[epoch, 'test', ssim_avg, psnr_avg]`` to ``each_epoch.csv`` after the ``train`` row; the pass leaves
-the training run bit-identical (``eval_pass``).
+the training run bit-identical (``eval_pass``).  With ``--ema_decay`` on, the same pass runs once more on
+the averaged generator (``Pix2PixModel.ema_scope``) and appends ``[epoch, 'test_ema', ssim_avg, psnr_avg]``
+after the ``test`` row; the checkpoint of each epoch then has its ``_net_G_ema`` file.
 """
 import argparse
 import csv
@@ -186,6 +188,12 @@ def main(argv=None, output_freq=100):
                 print("test (%s) ssim: %.4f psnr: %.3f" % (known.eval_phase, t_ssim, t_psnr))
                 with open(os.path.join(out, "each_epoch.csv"), "a", newline="") as f:
                     csv.writer(f).writerow([epoch, "test", t_ssim, t_psnr])
+                if getattr(model, "ema_on", False):   # the averaged generator, on the same split
+                    with model.ema_scope():
+                        e_ssim, e_psnr = eval_pass(model, opt, known.eval_phase)
+                    print("test_ema (%s) ssim: %.4f psnr: %.3f" % (known.eval_phase, e_ssim, e_psnr))
+                    with open(os.path.join(out, "each_epoch.csv"), "a", newline="") as f:
+                        csv.writer(f).writerow([epoch, "test_ema", e_ssim, e_psnr])
             print("saving the model at the end of epoch %d, iters %d" % (epoch, i + 1))
             model.save_networks(epoch)
             print("End of epoch %d / %d \t Time Taken: %d sec" % (epoch, opt.niter + opt.niter_decay,

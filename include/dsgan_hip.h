@@ -745,6 +745,16 @@ int dsgan_amp_check(const float* grad, long n, int* part, float* state, float ba
                     hipStream_t stream);
 int dsgan_adam_amp(float* p, const float* g, float* m, float* v, long n, double lr, double beta1, double beta2,
                    double eps, const float* state, hipStream_t stream);
+/* The generator's exponential moving average (--ema_decay) fused into the update: the two forms
+ * above, after which the same lane does ema.lerp_(p_new, (float)(1 - ema_decay)) (at::lerp's form).
+ * p, m, v get the bits of dsgan_adam / dsgan_adam_amp.  ema: n floats, not null; 0 <= ema_decay < 1.
+ * A step that dsgan_adam_amp_ema skips (state[1] != 0) leaves ema untouched as well. */
+int dsgan_adam_ema(float* p, const float* g, float* m, float* v, float* ema, long n, double lr, double beta1,
+                   double beta2, double eps, double ema_decay, int step, hipStream_t stream);
+int dsgan_adam_amp_ema(float* p, const float* g, float* m, float* v, float* ema, long n, double lr, double beta1,
+                       double beta2, double eps, double ema_decay, const float* state, hipStream_t stream);
+/* exchange two buffers of n floats that do not overlap, in place: one launch, no temporary */
+int dsgan_swap(float* a, float* b, long n, hipStream_t stream);
 
 #ifdef __cplusplus
 }
