@@ -217,6 +217,9 @@ SIGNATURES = {
     "dsgan_adam_ema": [P, P, P, P, P, L, D, D, D, D, D, I, S],
     "dsgan_adam_amp_ema": [P, P, P, P, P, L, D, D, D, D, D, P, S],
     "dsgan_swap": [P, P, L, S],
+    # fingerprint.hip
+    "dsgan_fingerprint_parts": [],
+    "dsgan_fingerprint": [P, L, P, L, P, S],
 }
 
 _lib = None

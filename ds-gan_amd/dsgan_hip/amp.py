@@ -65,3 +65,27 @@ class LossScaler:
 
     def applied_steps(self):
         return int(self.state[4].item())
+
+    # resumable training (synchronises)
+    def state_dict(self):
+        """The five state floats (a CPU tensor) and the constants of the rule."""
+        return {"state": self.state.detach().cpu().clone(), "growth": self.growth, "backoff": self.backoff,
+                "interval": self.interval, "unit": bool(self.unit)}
+
+    def load_state_dict(self, sd):
+        """In place: ``state`` keeps its device buffer (captured graphs hold the pointer).  A unit-scale
+        guard does not take a loss scaler's state, nor the reverse; growth / backoff / interval are
+        constants of the run (captured graphs hold them as kernel arguments), so a file with other
+        values is refused too."""
+        if bool(sd["unit"]) != bool(self.unit):
+            raise ValueError("LossScaler: the file holds a %s, this run has a %s"
+                             % tuple("unit-scale non-finite guard" if u else "dynamic loss scaler"
+                                     for u in (sd["unit"], self.unit)))
+        for key, mine in (("growth", self.growth), ("backoff", self.backoff), ("interval", self.interval)):
+            if float(sd[key]) != float(mine):
+                raise ValueError("LossScaler: %s %r in the file, %r in this run" % (key, sd[key], mine))
+        st = sd["state"]
+        if tuple(st.shape) != (5,):
+            raise ValueError("LossScaler: a state of shape %s, expected (5,)" % (tuple(st.shape),))
+        with torch.no_grad():
+            self.state.copy_(st.to(torch.float32))

@@ -43,6 +43,32 @@ def all_ranks_true(flag, device):
     return bool(t.item())
 
 
+def fingerprint_mismatches(rows, names):
+    """``rows``: int64 [world, K], row r = rank r's K fingerprints.  The (rank, name) pairs that differ
+    from rank 0's row, in order (a pure function)."""
+    return [(r, names[k]) for r in range(1, rows.shape[0]) for k in range(rows.shape[1])
+            if int(rows[r, k]) != int(rows[0, k])]
+
+
+def require_same_fingerprints(fps, names, device="cpu"):
+    """Every rank holds the same state where it must: ``fps`` is this rank's CPU int64 tensor of K
+    fingerprints (dsgan_hip.functional.fingerprint values, two's complement), ``names`` their buffers.
+    One eager all-gather (never inside a capture); a rank that differs from rank 0 makes EVERY rank raise
+    RuntimeError naming the buffers, so that no rank goes on to write or to wait."""
+    if fps.dtype != torch.int64 or fps.dim() != 1 or fps.numel() != len(names) or fps.is_cuda:
+        raise ValueError("require_same_fingerprints: a CPU int64 vector with one entry per name required")
+    W = world_size()
+    if W == 1:
+        return
+    mine = fps.to(device) if backend() == "nccl" else fps
+    rows = [torch.empty_like(mine) for _ in range(W)]
+    dist.all_gather(rows, mine)
+    bad = fingerprint_mismatches(torch.stack(rows).cpu(), list(names))
+    if bad:
+        raise RuntimeError("the ranks' training state differs from rank 0's: "
+                           + ", ".join("%s on rank %d" % (n, r) for r, n in bad))
+
+
 def broadcast_params(flat, src=0):
     if world_size() > 1:
         dist.broadcast(flat.data, src)

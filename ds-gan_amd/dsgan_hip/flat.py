@@ -57,6 +57,79 @@ class FlatParams:
         fill_(self.grad, 0.0)
 
 
+# ---- the moments in torch.optim.Adam's state-dict format (pure functions over CPU tensors) ----
+# what torch.optim.Adam's own param_groups carry beside lr / betas / eps: written so that the
+# reference's torch.optim.Adam(net.parameters(), ...) takes the file with its own load_state_dict
+_TORCH_ADAM_GROUP = dict(weight_decay=0, amsgrad=False, maximize=False, foreach=None, capturable=False,
+                         differentiable=False, fused=None)
+
+
+def adam_state_to_torch(m, v, slots, step, group):
+    """torch.optim.Adam's ``state_dict()`` from the flat moments.  ``m`` / ``v``: flat fp32 CPU tensors;
+    ``slots``: one (offset, shape) per parameter in ``module.parameters()`` order (the state index);
+    ``step``: the applied steps, one number for every parameter (a python scalar tensor each, as torch
+    keeps it); ``group``: the param group (lr, betas, eps; ``params`` is replaced by the indices)."""
+    state = {}
+    for i, (off, shape) in enumerate(slots):
+        k = int(torch.Size(shape).numel())
+        state[i] = {"step": torch.tensor(float(step), dtype=torch.float32),
+                    "exp_avg": m[off:off + k].view(shape).clone(),
+                    "exp_avg_sq": v[off:off + k].view(shape).clone()}
+    g = dict(_TORCH_ADAM_GROUP)
+    g.update({k: (list(x) if isinstance(x, tuple) else x) for k, x in group.items() if k != "params"})
+    g["params"] = list(range(len(slots)))
+    return {"state": state, "param_groups": [g]}
+
+
+def adam_state_from_torch(sd, slots, numel, group, names=None):
+    """(m, v, step) from a torch.optim.Adam ``state_dict()``: flat fp32 CPU tensors of ``numel`` elements
+    (zero outside the slots, as the kernel leaves the padding) and the one common step.  Raises, with the
+    parameters' ``names`` (else their indices), on a missing entry, a shape mismatch, differing steps, or
+    betas / eps other than ``group``'s.  With names on both sides (``sd['param_names']``) entries pair up
+    by name; else by index.  An empty ``state`` (an optimizer that never stepped) is step 0, zero moments."""
+    named = names is not None
+    names = list(names) if named else [str(i) for i in range(len(slots))]
+    groups = sd["param_groups"]
+    if len(groups) != 1 or len(groups[0]["params"]) != len(slots):
+        raise ValueError("optimizer state: %d param group(s) over %s parameters, this optimizer has one group of %d"
+                         % (len(groups), [len(g["params"]) for g in groups], len(slots)))
+    for key in ("betas", "eps"):
+        a, b = groups[0][key], group[key]
+        if (tuple(float(x) for x in a) != tuple(float(x) for x in b)) if key == "betas" else float(a) != float(b):
+            raise ValueError("optimizer state: %s %r in the file, %r in this run" % (key, a, b))
+    index = list(groups[0]["params"])
+    saved = sd.get("param_names")
+    if named and saved is not None:
+        if sorted(saved) != sorted(names):
+            raise ValueError("optimizer state: parameter names differ: only in the file %s, only in this run %s"
+                             % (sorted(set(saved) - set(names)), sorted(set(names) - set(saved))))
+        index = [index[list(saved).index(n)] for n in names]
+    state = sd["state"]
+    m, v = torch.zeros(numel, dtype=torch.float32), torch.zeros(numel, dtype=torch.float32)
+    if not state:
+        return m, v, 0
+    missing = [n for n, i in zip(names, index) if i not in state]
+    if missing:
+        raise ValueError("optimizer state: no entry for %s" % missing)
+    steps = {n: float(state[i]["step"]) for n, i in zip(names, index)}
+    if len(set(steps.values())) != 1:
+        raise ValueError("optimizer state: the parameters' step counts differ (one flat update needs one): %s"
+                         % sorted(set(steps.values())))
+    step = next(iter(steps.values()))
+    if step != int(step) or step < 0:
+        raise ValueError("optimizer state: step %r is not a whole number" % step)
+    bad = ["%s: %s %s in the file vs %s" % (n, key, tuple(state[i][key].shape), tuple(shape))
+           for n, i, (_, shape) in zip(names, index, slots) for key in ("exp_avg", "exp_avg_sq")
+           if tuple(state[i][key].shape) != tuple(shape)]
+    if bad:
+        raise ValueError("optimizer state: size mismatch for " + "; ".join(bad))
+    for i, (off, shape) in zip(index, slots):
+        k = int(torch.Size(shape).numel())
+        m[off:off + k].copy_(state[i]["exp_avg"].detach().reshape(-1).to("cpu", torch.float32))
+        v[off:off + k].copy_(state[i]["exp_avg_sq"].detach().reshape(-1).to("cpu", torch.float32))
+    return m, v, int(step)
+
+
 class FlatAdam(torch.optim.Optimizer):
     """torch.optim.Adam (amsgrad=False, weight_decay=0) over a FlatParams buffer in one kernel.
 
@@ -100,6 +173,38 @@ class FlatAdam(torch.optim.Optimizer):
 
     def zero_grad(self, set_to_none=False):
         self.flat.zero_grad()
+
+    # ---- torch.optim.Adam's state-dict format (resumable training; synchronises) ----
+    def _slots(self):
+        offs = {id(p): off for p, off, _ in self.flat.layout}
+        return [(offs[id(p)], tuple(p.shape)) for p in self.flat.params]
+
+    def applied_steps(self):
+        """The update count the bias corrections use: the scaler's device counter, else step_count."""
+        return self.scaler.applied_steps() if self.scaler is not None else self.step_count
+
+    def state_dict(self):
+        """``torch.optim.Adam``'s: {'state': {i: {'step', 'exp_avg', 'exp_avg_sq'}}, 'param_groups': [...]},
+        i over ``flat.params`` (``module.parameters()`` order), CPU tensors of the parameters' shapes; a
+        ``torch.optim.Adam`` over the same parameters loads it.  The EMA buffer is not part of it (it is a
+        checkpoint file of its own)."""
+        return adam_state_to_torch(self.m.cpu(), self.v.cpu(), self._slots(), self.applied_steps(),
+                                   self.param_groups[0])
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict, names=None):
+        """From this class's or ``torch.optim.Adam``'s state dict, in place: ``m`` and ``v`` keep their
+        device buffers (captured graphs hold the pointers) and the step goes back to the counter in use
+        (the scaler's ``state[4]``, else ``step_count``).  ``lr`` is NOT restored: the scheduler built from
+        ``--epoch_count`` owns it.  ``names``: the parameters' names, for the messages and to pair entries
+        with a file that carries ``param_names``."""
+        m, v, step = adam_state_from_torch(state_dict, self._slots(), self.flat.numel, self.param_groups[0], names)
+        self.m.copy_(m)
+        self.v.copy_(v)
+        if self.scaler is not None:
+            self.scaler.state[4:5].copy_(torch.tensor([float(step)]))
+        else:
+            self.step_count = step
 
     @torch.no_grad()
     def step(self, closure=None):

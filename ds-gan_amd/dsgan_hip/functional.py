@@ -809,6 +809,18 @@ def zeros(shape, like):
     return fill_(torch.empty(shape, device=like.device, dtype=torch.float32), 0.0)
 
 
+def fingerprint(t):
+    """The 64-bit fingerprint (a python int in [0, 2^64)) of a contiguous device tensor of a 4-byte
+    element type, over its bit patterns (dsgan_fingerprint: -0.0 differs from 0.0, NaN payloads
+    count).  Synchronises; meant for checkpoint save / load time, not for the step."""
+    if not t.is_contiguous() or t.element_size() != 4:
+        raise ValueError("fingerprint: a contiguous tensor of a 4-byte element type required, got %s %s"
+                         % (t.dtype, "contiguous" if t.is_contiguous() else "strided"))
+    part = torch.empty(int(_lib.load().dsgan_fingerprint_parts()) + 1, device=t.device, dtype=torch.int64)
+    call("dsgan_fingerprint", ptr(t), t.numel(), ptr(part), part.numel() - 1, ptr(part[-1:]), stream())
+    return int(part[-1].item()) & (2 ** 64 - 1)
+
+
 def copy_multi(pairs):
     """dst <- src for a list of (dst, src) dense fp32 tensors of equal size, one launch per 32 pairs."""
     if not pairs:

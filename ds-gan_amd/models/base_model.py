@@ -13,6 +13,51 @@ import torch
 from . import networks
 
 
+def atomic_save(obj, path):
+    """torch.save under a temporary name in the same directory, then os.replace: a reader sees the old
+    file or the whole new one, never a part."""
+    tmp = "%s.tmp%d" % (path, os.getpid())
+    try:
+        torch.save(obj, tmp)
+        os.replace(tmp, path)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+
+
+def rng_state_dict(device=None):
+    """The python ``random``, numpy, torch-CPU and (``device`` given) torch-device generator states as
+    tensors and plain lists, so that the file loads with ``torch.load(weights_only=True)``."""
+    import random
+    import numpy as np
+    ver, words, gauss = random.getstate()
+    kind, keys, pos, has_gauss, cached = np.random.get_state()
+    out = {"python": [ver, list(words), gauss],
+           "numpy": {"kind": str(kind), "keys": torch.from_numpy(keys.astype(np.int64)), "pos": int(pos),
+                     "has_gauss": int(has_gauss), "cached_gaussian": float(cached)},
+           "torch_cpu": torch.get_rng_state().clone()}
+    if device is not None and torch.device(device).type == "cuda":
+        out["torch_device"] = torch.cuda.get_rng_state(device).clone()
+    return out
+
+
+def load_rng_state_dict(sd, device=None):
+    import random
+    import numpy as np
+    ver, words, gauss = sd["python"]
+    random.setstate((ver, tuple(words), gauss))
+    n = sd["numpy"]
+    np.random.set_state((n["kind"], n["keys"].numpy().astype(np.uint32), n["pos"], n["has_gauss"], n["cached_gaussian"]))
+    torch.set_rng_state(sd["torch_cpu"].to("cpu", torch.uint8))
+    if device is not None and "torch_device" in sd and torch.device(device).type == "cuda":
+        torch.cuda.set_rng_state(sd["torch_device"].to("cpu", torch.uint8), device)
+
+
+def train_state_filename(which_epoch, rank=0):
+    """Rank 0's file holds the whole state; rank r > 0 adds what is its own (pool, RNGs, dropout counters)."""
+    return "%s_train_state.pth" % which_epoch if rank == 0 else "%s_train_state_rank%d.pth" % (which_epoch, rank)
+
+
 class BaseModel:
     @staticmethod
     def modify_commandline_options(parser, is_train):
@@ -137,6 +182,46 @@ class BaseModel:
                     for k, v in state_dict.items():
                         if k in own:
                             own[k].copy_(v.to(own[k].device, own[k].dtype))
+
+    # ---- resumable training: everything beside the weights (--save_state / --resume) ----
+    RANK_STATE_KEYS = ("version", "epoch", "world_size", "precision", "pool", "dropout", "rng")
+
+    def train_state_dict(self):
+        """What a model needs beside its network files to continue bit for bit (Pix2PixModel)."""
+        raise NotImplementedError("%s keeps no resumable training state" % self.name())
+
+    def load_train_state_dict(self, sd, own):
+        raise NotImplementedError("%s keeps no resumable training state" % self.name())
+
+    def save_train_state(self, which_epoch):
+        """'{epoch}_train_state.pth' in save_dir, written after the network files of that epoch and
+        atomically (atomic_save), so that a job killed mid-save leaves the previous epoch resumable.
+        Under ``torchrun`` EVERY rank calls this (train_state_dict compares the ranks' fingerprints with one
+        collective): rank 0 writes the whole state, rank r > 0 '{epoch}_train_state_rank{r}.pth' with what is
+        its own (RANK_STATE_KEYS)."""
+        from dsgan_hip import dist as hdist
+        sd = self.train_state_dict()
+        sd["epoch"] = which_epoch
+        r = hdist.rank()
+        if r > 0:
+            sd = {k: sd[k] for k in self.RANK_STATE_KEYS}
+        os.makedirs(self.save_dir, exist_ok=True)
+        path = os.path.join(self.save_dir, train_state_filename(which_epoch, r))
+        atomic_save(sd, path)
+        return path
+
+    def load_train_state(self, which_epoch):
+        """After load_networks (and load_ema) of the same epoch: restores the state in place and checks the
+        buffers' fingerprints against the file's.  Every rank reads rank 0's file and, r > 0, its own."""
+        from dsgan_hip import dist as hdist
+        path = os.path.join(self.save_dir, train_state_filename(which_epoch))
+        print("loading the training state from %s" % path)
+        sd = torch.load(path, map_location="cpu", weights_only=True)
+        own = sd
+        if hdist.rank() > 0:
+            own = torch.load(os.path.join(self.save_dir, train_state_filename(which_epoch, hdist.rank())),
+                             map_location="cpu", weights_only=True)
+        self.load_train_state_dict(sd, own)
 
     def print_networks(self, verbose):
         print("---------- Networks initialized -------------")

@@ -42,6 +42,10 @@ Deliberate, documented deviations:
     does not average, a graph replay does, and every rank computes the same average without any
     exchange.  ``ema_scope()`` makes ``netG`` the averaged generator for a while; save_networks
     writes it as ``{epoch}_useSE_net_G_ema.pth``.  BatchNorm running buffers are not averaged.
+  * save_train_state / load_train_state (train.py --save_state / --resume): everything a run needs beside
+    the network files to continue bit for bit -- Adam's moments and steps (torch.optim.Adam's format), the
+    scalers, the ImagePool, the dropout counters, step_calls, the RNGs -- restored in place and checked by
+    device-side fingerprints of the flat buffers (dsgan_fingerprint); the reference saves weights only.
 """
 import contextlib
 import os
@@ -55,7 +59,7 @@ from dsgan_hip import dist as hdist
 from dsgan_hip.flat import FlatParams, FlatAdam
 from dsgan_hip.amp import LossScaler
 from util.image_pool import ImagePool
-from .base_model import BaseModel
+from .base_model import BaseModel, rng_state_dict, load_rng_state_dict
 from . import networks
 
 # backward_D runs D once on the fake and real batches stacked (DSGAN_D_BATCH=0: two passes, as the
@@ -544,6 +548,106 @@ class Pix2PixModel(BaseModel):
                     raise RuntimeError("EMA checkpoint %s: size mismatch for %s: %s vs model %s"
                                        % (path, k, tuple(sd[k].shape), tuple(p.shape)))
                 views[id(p)].copy_(sd[k].to(self.device, torch.float32))
+
+    # ---- resumable training (--save_state / --resume) ----
+    def _state_buffers(self):
+        """(name, flat device buffer): what the state file fingerprints, and the ranks must agree on."""
+        out = [("G.data", self.flatG.data), ("D.data", self.flatD.data),
+               ("G.exp_avg", self.optimizer_G.m), ("G.exp_avg_sq", self.optimizer_G.v),
+               ("D.exp_avg", self.optimizer_D.m), ("D.exp_avg_sq", self.optimizer_D.v)]
+        if self.ema_on:
+            out.append(("G.ema", self.optimizer_G.ema))
+        return out
+
+    def _param_names(self, net, flat):
+        names = {id(p): k for k, p in net.named_parameters()}
+        return [names[id(p)] for p in flat.params]
+
+    def _layout_signature(self):
+        """[name, offset, numel] per parameter in buffer order, for each flat buffer: equal signatures mean
+        that a flat buffer's fingerprint speaks about the same bits."""
+        out = {}
+        for key, net, flat in (("G", self.netG, self.flatG), ("D", self.netD, self.flatD)):
+            names = {id(p): k for k, p in net.named_parameters()}
+            out[key] = [[names[id(p)], int(off), int(k)] for p, off, k in flat.layout]
+        return out
+
+    def _dropout_blocks(self):
+        return [(k, m) for k, m in self.netG.named_modules() if "drop_counter" in getattr(m, "_buffers", {})]
+
+    def train_state_dict(self):
+        """Both optimizers (torch.optim.Adam's format, plus ``param_names``), both scalers, the ImagePool, the
+        U-Net's dropout counters, step_calls, the four RNG states, world size, precision, the flat buffers'
+        layout and the fingerprints of the weights, the moments and the EMA.  Synchronises.  Under
+        ``torchrun`` a collective: the ranks compare their fingerprints (RuntimeError on every rank naming
+        the buffer when one differs from rank 0's)."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("train_state_dict: a HIP graph capture is in progress")
+        bufs = self._state_buffers()
+        fps = {n: HF.fingerprint(t) for n, t in bufs}
+        signed = torch.tensor([v - (1 << 64) if v >= (1 << 63) else v for v in fps.values()], dtype=torch.int64)
+        hdist.require_same_fingerprints(signed, list(fps), self.device)
+        sd = {"version": 1, "world_size": hdist.world_size(), "precision": HF.get_precision(),
+              "step_calls": dict(self.step_calls), "layout": self._layout_signature(),
+              "fingerprints": {n: "%016x" % v for n, v in fps.items()},
+              "pool": self.fake_AB_pool.state_dict(), "rng": rng_state_dict(self.device),
+              "dropout": {k: {"counter": int(m.drop_counter.item()), "seed": int(m.drop_seed),
+                              "stream": int(m.drop_stream)} for k, m in self._dropout_blocks()}}
+        for key, net, flat, optim, sc in (("G", self.netG, self.flatG, self.optimizer_G, self.scaler_G),
+                                          ("D", self.netD, self.flatD, self.optimizer_D, self.scaler_D)):
+            sd["optimizer_" + key] = dict(optim.state_dict(), param_names=self._param_names(net, flat))
+            sd["scaler_" + key] = sc.state_dict() if sc is not None else None
+        return sd
+
+    def load_train_state_dict(self, sd, own):
+        """``sd``: rank 0's state; ``own``: this rank's (``sd`` itself on rank 0).  Everything is copied into
+        the existing device buffers (captured graphs hold their pointers).  The weights and the EMA are not
+        here: load_networks / load_ema read them, and their fingerprints below check that those files
+        belong to this state."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("load_train_state_dict: a HIP graph capture is in progress")
+        if int(sd["world_size"]) != hdist.world_size():
+            raise RuntimeError("the training state was saved by %d rank(s), this run has %d: not resumable (the "
+                               "ranks' batches, pools and RNG streams would differ)"
+                               % (sd["world_size"], hdist.world_size()))
+        if sd["precision"] != HF.get_precision():
+            raise RuntimeError("the training state was saved with --precision %s, this run uses %s: not resumable"
+                               % (sd["precision"], HF.get_precision()))
+        for key, net, flat, optim, sc in (("G", self.netG, self.flatG, self.optimizer_G, self.scaler_G),
+                                          ("D", self.netD, self.flatD, self.optimizer_D, self.scaler_D)):
+            if (sd["scaler_" + key] is None) != (sc is None):
+                raise RuntimeError("the training state has %s scaler_%s state, this run has %s (--nonfinite_guard)"
+                                   % (("a", key, "no scaler") if sc is None else ("no", key, "one")))
+            optim.load_state_dict(sd["optimizer_" + key], names=self._param_names(net, flat))
+            if sc is not None:
+                sc.load_state_dict(sd["scaler_" + key])
+        self.step_calls = {k: int(v) for k, v in sd["step_calls"].items()}
+        self.fake_AB_pool.load_state_dict(own["pool"], device=self.device)
+        blocks = dict(self._dropout_blocks())
+        if sorted(blocks) != sorted(own["dropout"]):
+            raise RuntimeError("the training state holds dropout counters for %s, this generator has %s"
+                               % (sorted(own["dropout"]), sorted(blocks)))
+        for k, m in blocks.items():
+            d = own["dropout"][k]
+            if (m.drop_seed, m.drop_stream) != (d["seed"], d["stream"]):
+                # captured graphs hold the seed and the stream id as kernel arguments: capture again
+                self._graphs, self._graph_warm = {}, set()
+            with torch.no_grad():
+                m.drop_counter.fill_(int(d["counter"]))
+            m.drop_seed, m.drop_stream = int(d["seed"]), int(d["stream"])
+        load_rng_state_dict(own["rng"], self.device)
+        # verification: the restored buffers (and the weight files loaded beside this state) hash to the file's
+        if sd["layout"] != self._layout_signature():
+            print("train state: the flat buffers' layout differs from the file's (another buffer order): "
+                  "fingerprints not compared")
+            return
+        for name, t in self._state_buffers():
+            want = sd["fingerprints"].get(name)
+            got = "%016x" % HF.fingerprint(t)
+            if want is not None and want != got:
+                raise RuntimeError("train state: buffer %s has fingerprint %s after loading, the file says %s: "
+                                   "the weight / EMA files or the state file are not the ones saved together"
+                                   % (name, got, want))
 
     # ---- train.py helpers (DSGAN/models/pix2pix_model.py:292-310) ----
     def get_img_tir(self, input):

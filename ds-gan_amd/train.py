@@ -23,12 +23,21 @@ scores the generator in eval mode on that split (evaluate.py's pass) and appends
 the training run bit-identical (``eval_pass``).  With ``--ema_decay`` on, the same pass runs once more on
 the averaged generator (``Pix2PixModel.ema_scope``) and appends ``[epoch, 'test_ema', ssim_avg, psnr_avg]``
 after the ``test`` row; the checkpoint of each epoch then has its ``_net_G_ema`` file.
+
+``--save_state 1`` (default 0): after each epoch's network files every rank also writes its training state
+(``save_train_state``: Adam's moments and step, the scalers, the ImagePool, the dropout counters, the RNGs),
+``--keep_states N`` (default 2) epochs of them are kept.  ``--resume`` (implies ``--save_state 1``) continues
+after the newest epoch whose state and network files are complete -- ``--continue_train``, ``--which_epoch``
+and ``--epoch_count`` are set from it -- or starts fresh when there is none, so one command line both starts
+and continues a run; the continued run is bit-identical to an uninterrupted one (README, "Resumable
+training").  ``--stop_after_epoch E`` leaves the loop once epoch E is saved, the schedule untouched.
 """
 import argparse
 import csv
 import math
 import os
 import random
+import re
 import sys
 import time
 
@@ -119,6 +128,32 @@ def eval_pass(model, opt, phase):
     return means[0], means[1]
 
 
+_STATE_RE = re.compile(r"^(\d+)_train_state(?:_rank(\d+))?\.pth$")
+
+
+def find_resume_epoch(names, world=1, ema=False):
+    """The newest epoch that can be resumed, or None: a pure function of the checkpoint directory's
+    listing ``names``.  An epoch counts when its state file(s) -- rank 0's, and under ``world`` ranks every
+    rank's -- and its network files (G and D, either naming load_networks reads; with ``ema`` the averaged
+    generator's too) are all there.  Temporary files of an interrupted save (another suffix) never match."""
+    names = set(names)
+    epochs = sorted((int(m.group(1)) for m in map(_STATE_RE.match, names) if m and m.group(2) is None), reverse=True)
+    nets = ["G", "D"] + (["G_ema"] if ema else [])
+    for e in epochs:
+        ranks = all("%d_train_state_rank%d.pth" % (e, r) in names for r in range(1, world))
+        files = all("%d_net_%s.pth" % (e, n) in names or "%d_useSE_net_%s.pth" % (e, n) in names for n in nets)
+        if ranks and files and "%d_train_state.pth" % e in names:
+            return e
+    return None
+
+
+def states_to_prune(names, keep):
+    """The state files (every rank's; nothing else) of all but the ``keep`` newest epochs that have any."""
+    found = [(int(m.group(1)), n) for n, m in ((n, _STATE_RE.match(n)) for n in names) if m]
+    kept = set(sorted({e for e, _ in found}, reverse=True)[:max(int(keep), 0)])
+    return sorted(n for e, n in found if e not in kept)
+
+
 def main(argv=None, output_freq=100):
     from data import CreateDataLoader
     from models import create_model
@@ -131,7 +166,15 @@ def main(argv=None, output_freq=100):
     ap.add_argument("--eval_freq", type=int, default=0,
                     help="every N epochs rank 0 scores the generator on --eval_phase (0: never)")
     ap.add_argument("--eval_phase", default="test_all/", help="the split of the per-epoch test pass")
+    ap.add_argument("--save_state", type=int, default=0, choices=[0, 1],
+                    help="1: after each epoch's save_networks also save_train_state (optimizers, scalers, pool, RNGs)")
+    ap.add_argument("--keep_states", type=int, default=2, help="state files of this many newest epochs are kept")
+    ap.add_argument("--stop_after_epoch", type=int, default=0,
+                    help="leave the epoch loop once this epoch is saved (0: off; the schedule is untouched)")
+    ap.add_argument("--resume", action="store_true",
+                    help="continue from the newest epoch with a complete state (else start fresh); implies --save_state 1")
     known, rest = ap.parse_known_args(argv)
+    save_state = bool(known.save_state) or known.resume
     rank, world, local = init_distributed()
     setup_seed(20)
     out = known.out
@@ -140,10 +183,22 @@ def main(argv=None, output_freq=100):
     opt = TrainOptions().parse(known.dataroot, out, rest)   # parse() sets checkpoints_dir = out/checkpoints
     if world > 1:
         opt.gpu_ids = [local]   # one process per GPU: this rank's device
+    resumed = None
+    if known.resume:
+        ckpt_dir = os.path.join(opt.checkpoints_dir, opt.name)
+        resumed = find_resume_epoch(os.listdir(ckpt_dir) if os.path.isdir(ckpt_dir) else [], world,
+                                    float(getattr(opt, "ema_decay", 0.0) or 0.0) > 0.0)
+        if resumed is None:
+            print("--resume: no complete training state in %s, starting fresh" % ckpt_dir)
+        else:
+            print("--resume: continuing after epoch %d" % resumed)
+            opt.continue_train, opt.which_epoch, opt.epoch_count = True, str(resumed), resumed + 1
     dataset = CreateDataLoader(opt, "train").load_data()
     print("#training images = %d" % len(dataset))
     model = create_model(opt)
     model.setup(opt)
+    if resumed is not None:   # after the weights (and the EMA) of that epoch: their fingerprints are checked
+        model.load_train_state(resumed)
     metrics = TrainMetrics(model.device)
     guard = NonfiniteMonitor(model)
     history = []
@@ -200,7 +255,14 @@ def main(argv=None, output_freq=100):
                                                                     time.time() - epoch_start_time))
         if world > 1:
             dist.barrier()
+        if save_state:   # every rank (its own file; the ranks' fingerprints are compared), after the network files
+            model.save_train_state(epoch)
+            if rank == 0:
+                for name in states_to_prune(os.listdir(model.save_dir), known.keep_states):
+                    os.remove(os.path.join(model.save_dir, name))
         model.update_learning_rate()
+        if known.stop_after_epoch > 0 and epoch >= known.stop_after_epoch:
+            break
     return model, history
 
 

@@ -28,6 +28,44 @@ class ImagePool:
         """The stored images, reference order (views of the resident pool)."""
         return [self.store[i:i + 1] for i in range(self.num_imgs)] if self.pool_size > 0 and self.store is not None else []
 
+    # ---- resumable training ----
+    def state_dict(self):
+        """pool_size, num_imgs, the filled slots (one CPU tensor, None while the pool is empty) and the
+        pool's private ``random.Random`` state as plain lists (None when it draws from the global
+        ``random``, whose state the caller saves)."""
+        n = self.num_imgs if self.pool_size > 0 else 0
+        rng = None
+        if self.rng is not random:
+            ver, words, gauss = self.rng.getstate()
+            rng = [ver, list(words), gauss]
+        return {"pool_size": self.pool_size, "num_imgs": n,
+                "images": self.store[:n].detach().cpu().clone() if n > 0 else None, "rng": rng}
+
+    def load_state_dict(self, sd, device=None):
+        """In place: a resident pool keeps its tensor (a shape or dtype mismatch raises); a pool that has
+        not seen a query yet allocates it on ``device``, as its first query would have."""
+        if int(sd["pool_size"]) != int(self.pool_size):
+            raise ValueError("ImagePool: pool_size %d in the file, %d in this run" % (sd["pool_size"], self.pool_size))
+        if (sd["rng"] is None) != (self.rng is random):
+            raise ValueError("ImagePool: the file %s a private RNG state, this pool %s one"
+                             % ("has" if sd["rng"] is not None else "lacks", "lacks" if self.rng is random else "has"))
+        n, imgs = int(sd["num_imgs"]), sd["images"]
+        if n > 0:
+            if imgs.shape[0] != n or n > self.pool_size:
+                raise ValueError("ImagePool: %d images for num_imgs %d, pool_size %d" % (imgs.shape[0], n, self.pool_size))
+            if self.store is not None and (self.store.shape[1:] != imgs.shape[1:] or self.store.dtype != imgs.dtype):
+                raise ValueError("ImagePool: images of shape %s %s in the file, the pool holds shape %s %s"
+                                 % (tuple(imgs.shape[1:]), imgs.dtype, tuple(self.store.shape[1:]), self.store.dtype))
+            if self.store is None:
+                self.store = torch.empty((self.pool_size,) + tuple(imgs.shape[1:]), dtype=imgs.dtype,
+                                         device=device if device is not None else imgs.device)
+            self.store[:n].copy_(imgs)
+        if self.pool_size > 0:
+            self.num_imgs = n
+        if sd["rng"] is not None:
+            ver, words, gauss = sd["rng"]
+            self.rng.setstate((ver, tuple(words), gauss))
+
     def query(self, images, out=None):
         """The reference's query; ``out`` (optional, images' shape): the result is written there (the
         CUDA-graph step's static buffer between its two captured halves)."""

@@ -756,6 +756,16 @@ int dsgan_adam_amp_ema(float* p, const float* g, float* m, float* v, float* ema,
 /* exchange two buffers of n floats that do not overlap, in place: one launch, no temporary */
 int dsgan_swap(float* a, float* b, long n, hipStream_t stream);
 
+/* ---- state fingerprint (fingerprint.hip): resumable training's "restored exactly" check ---- */
+/* out[0] = sum over i < n of mix((i << 32) | word_i) mod 2^64 over the n 32-bit words at buf, mix = the
+ * splitmix64 finaliser: bit patterns, not float values (-0.0 differs from 0.0, NaN payloads count);
+ * independent of the grid.  0 <= n < 2^32; n == 0 writes 0.  A 16-byte aligned buf is read with
+ * 16-byte loads, any other 4-byte aligned buf word by word.  part: scratch of part_elems >=
+ * dsgan_fingerprint_parts() 64-bit words (the per-block partial sums).  The buffer is only read. */
+long dsgan_fingerprint_parts(void);
+int dsgan_fingerprint(const void* buf, long n, unsigned long long* part, long part_elems, unsigned long long* out,
+                      hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
