@@ -177,6 +177,9 @@ SIGNATURES = {
     "dsgan_images_to_u8": [P, I, P, I, P, I, I, I, I, P, S],
     "dsgan_ssim_eval_parts": [I, I, I, I],
     "dsgan_ssim_eval": [P, P, F, F, I, I, I, I, P, F, F, I, P, P, S],
+    # tiles.hip
+    "dsgan_u8_tiles": [P, I, I, P, I, P, I, I, I, I, I, I, P, S],
+    "dsgan_tiles_blend": [P, I, I, I, P, I, P, I, I, I, I, P, S],
     # lsgan.hip
     "dsgan_sigmoid_fwd": [P, L, P, S],
     "dsgan_sigmoid_bwd": [P, P, L, P, I, S],

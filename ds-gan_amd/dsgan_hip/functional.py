@@ -2603,6 +2603,50 @@ def images_to_u8(*imgs):
     return out
 
 
+def _origins(oy, ox, dev):
+    """The two device int32 origin arrays of a tile plan (a TilePlan's, or anything as_tensor takes)."""
+    out = []
+    for o in (oy, ox):
+        o = torch.as_tensor(o, dtype=torch.int32).to(dev).contiguous()
+        if o.dim() != 1 or o.numel() == 0:
+            raise ValueError("tile origins: a non-empty 1-D list per axis, got shape %s" % (tuple(o.shape),))
+        out.append(o)
+    return out
+
+
+def u8_tiles(frame_u8, oy, ox, th, tw, t0=0, T=None, gray=False):
+    """fp32 [T, 3|1, th, tw]: tiles t0 .. t0+T-1 (t = iy*nx + ix, corner (oy[iy], ox[ix])) of one uint8
+    [H, W, 3] device frame, converted as ``data.to_images`` converts a crop (bit-exact, no flip)."""
+    if frame_u8.dim() != 3 or frame_u8.shape[2] != 3 or frame_u8.dtype != torch.uint8:
+        raise ValueError("u8_tiles: a uint8 (H,W,3) frame required, got %s %s" % (tuple(frame_u8.shape), frame_u8.dtype))
+    frame_u8 = frame_u8.contiguous()
+    oy, ox = _origins(oy, ox, frame_u8.device)
+    H, W, _ = frame_u8.shape
+    T = oy.numel() * ox.numel() - t0 if T is None else int(T)
+    out = torch.empty((max(T, 0), 1 if gray else 3, int(th), int(tw)), device=frame_u8.device, dtype=torch.float32)
+    call("dsgan_u8_tiles", ptr(frame_u8), H, W, ptr(oy), oy.numel(), ptr(ox), ox.numel(), int(th), int(tw), int(t0), T,
+         int(bool(gray)), ptr(out), stream())
+    return out
+
+
+def tiles_blend(tiles, oy, ox, overlap, H, W):
+    """fp32 [C, H, W]: the [ny*nx, C, th, tw] tiles of a plan blended into one frame.  Every pixel is the
+    mean of the tiles that cover it under the integer ramp weight w1(y-oy) * w1(x-ox), w1(i) = min(i+1, L-i,
+    overlap), summed iy then ix ascending in fp32 (``dsgan_tiles_blend``); a pixel one tile covers is that
+    tile's value bit for bit."""
+    if tiles.dim() != 4 or tiles.dtype != torch.float32:
+        raise ValueError("tiles_blend: fp32 (T,C,th,tw) tiles required, got %s %s" % (tuple(tiles.shape), tiles.dtype))
+    tiles = tiles.detach().contiguous()
+    oy, ox = _origins(oy, ox, tiles.device)
+    T, C, th, tw = tiles.shape
+    if T != oy.numel() * ox.numel():
+        raise ValueError("tiles_blend: %d tiles for a %d x %d plan" % (T, oy.numel(), ox.numel()))
+    out = torch.empty((C, max(int(H), 0), max(int(W), 0)), device=tiles.device, dtype=torch.float32)
+    call("dsgan_tiles_blend", ptr(tiles), C, th, tw, ptr(oy), oy.numel(), ptr(ox), ox.numel(), int(overlap), int(H), int(W),
+         ptr(out), stream())
+    return out
+
+
 def ssim_eval_affine(real, fake, a=0.5, b=0.5, data_range=1.0, size_average=True, nonnegative=False):
     """Gaussian SSIM of (a*real+b, a*fake+b) (DSGAN/MS_SSIM.py:95-150), evaluation only: the per-image
     values [N] (channel mean of the plane means, relu'd per plane when ``nonnegative``) or their mean."""

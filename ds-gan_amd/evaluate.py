@@ -19,6 +19,15 @@ raw generator's file and writes to ``<phase>_<which_epoch>_ema/``, beside the ra
 file it fails, naming the paths it tried.  Evaluation is single-process (WORLD_SIZE > 1 is refused), batches are
 taken in order and never flipped, and ``--aspect_ratio`` other than 1.0 (the reference visualiser's
 resize) is refused.  The seed is 20, as in train.py.
+
+``--full_frame [--tile_overlap P]`` colourises whole frames instead of one fineSize crop per file: each file
+is read as it is (data/frame_dataset.py: no crop, any size not smaller than the tile), cut on the device into
+overlapping ``fineSize_h x fineSize_w`` tiles (dsgan_hip/tiling.py; P pixels of overlap, 32 by default, at most
+half a tile), the tiles go through the generator in chunks of at most ``--batchSize`` tiles of that frame, and
+the outputs are blended back under a linear ramp over the overlap (dsgan_tiles_blend).  Rows, panels and the
+CSV are then per frame, at the frame's size, in ``<phase>_<which_epoch>_full/`` (``..._full_ema/`` with
+``--use_ema``), beside the plain results.  Every tile is normalised by its own InstanceNorm statistics, as
+every training crop was; the ramp hides the difference.
 """
 import argparse
 import copy
@@ -34,12 +43,12 @@ if HERE not in sys.path:
 import torch  # noqa: E402
 
 
-def results_dir(opt, out, use_ema=False):
-    """<results_dir>/<name>/<phase>_<which_epoch>, with ``_ema`` appended for the averaged generator; a
-    relative --results_dir is taken under ``out``."""
+def results_dir(opt, out, use_ema=False, full_frame=False):
+    """<results_dir>/<name>/<phase>_<which_epoch>, with ``_full`` appended for whole frames and ``_ema`` for
+    the averaged generator; a relative --results_dir is taken under ``out``."""
     root = opt.results_dir if os.path.isabs(opt.results_dir) else os.path.join(out, opt.results_dir)
     leaf = "%s_%s" % (opt.phase.strip("/\\").replace("/", "_"), opt.which_epoch)
-    return os.path.join(root, opt.name, leaf + ("_ema" if use_ema else ""))
+    return os.path.join(root, opt.name, leaf + ("_full" if full_frame else "") + ("_ema" if use_ema else ""))
 
 
 def ema_checkpoint(save_dir, which_epoch):
@@ -52,7 +61,11 @@ def ema_checkpoint(save_dir, which_epoch):
                             % " and ".join(paths))
 
 
-def check_options(opt):
+def check_options(opt, tile_overlap=None):
+    """Refuse what evaluate.py does not do; ``tile_overlap`` is --tile_overlap of a --full_frame run."""
+    if tile_overlap is not None:
+        from dsgan_hip.tiling import check_overlap
+        check_overlap(tile_overlap, opt.fineSize_h, opt.fineSize_w)
     if float(opt.aspect_ratio) != 1.0:
         raise ValueError("evaluate.py writes the generator's pixels: --aspect_ratio %s (the reference visualiser's "
                          "resize) is not supported, only 1.0" % opt.aspect_ratio)
@@ -117,6 +130,42 @@ def run_pass(netG, dataset, AtoB=True, how_many=None, metrics=None, on_batch=Non
     return done
 
 
+def run_full_frame_pass(netG, frames, tile, overlap, batch, gray_in=False, gray_label=False, AtoB=True, how_many=None,
+                        metrics=None, on_batch=None):
+    """``run_pass`` on whole frames: ``frames`` yields FrameDataset items (uint8 frames of any size not smaller
+    than ``tile`` = (th, tw)); each goes through ``tiling.colorize_frame`` -- its own tiles only, in chunks of
+    at most ``batch`` -- and is scored and shown at its full size, one ``metrics.update`` per frame."""
+    from data import to_images
+    from dsgan_hip import tiling
+    flags = [(m, m.training) for m in netG.modules()]
+    netG.eval()
+    plans = {}
+    done = 0
+    try:
+        with torch.no_grad():
+            for data in frames:
+                labelled = "B_u8" in data
+                src = "A" if AtoB or not labelled else "B"
+                u8 = data[src + "_u8"].to("cuda", non_blocking=True)
+                H, W = int(u8.shape[0]), int(u8.shape[1])
+                if (H, W) not in plans:
+                    plans[(H, W)] = tiling.TilePlan(H, W, tile[0], tile[1], overlap)
+                fake = tiling.colorize_frame(netG, u8, plans[(H, W)], batch, gray_in).unsqueeze(0)
+                A = to_images(u8.unsqueeze(0), [0], gray_in)
+                B = to_images(data[("B" if AtoB else "A") + "_u8"].unsqueeze(0), [0], gray_label) if labelled else None
+                if metrics is not None and labelled:
+                    metrics.update(fake, B)
+                if on_batch is not None:
+                    on_batch(A, fake, B, [data[src + "_paths"]])
+                done += 1
+                if how_many is not None and done >= how_many:
+                    break
+    finally:
+        for m, t in flags:
+            m.training = t
+    return done
+
+
 def main(argv=None):
     from data import CreateDataLoader
     from dsgan_hip import functional as HF
@@ -134,16 +183,26 @@ def main(argv=None):
     ap.add_argument("--no_images", action="store_true", help="score only: write no PNG panels")
     ap.add_argument("--use_ema", action="store_true",
                     help="score the averaged generator (<which_epoch>_net_G_ema.pth) into <phase>_<which_epoch>_ema/")
+    ap.add_argument("--full_frame", action="store_true",
+                    help="colourise whole frames by overlapping fineSize tiles into <phase>_<which_epoch>_full/")
+    ap.add_argument("--tile_overlap", type=int, default=32, help="--full_frame: pixels two neighbouring tiles share")
     known, rest = ap.parse_known_args(argv)
+    overlap = known.tile_overlap if known.full_frame else None
+    if known.full_frame:   # before anything is written (parse() below creates the checkpoint directory)
+        check_options(TestOptions().gather_options(rest), overlap)
     setup_seed(20)
     opt = TestOptions().parse(known.dataroot, known.out, rest)
-    check_options(opt)
+    check_options(opt, overlap)
     opt = eval_options(opt)
     if known.use_ema:   # before anything is written
         ema_checkpoint(os.path.join(opt.checkpoints_dir, opt.name), opt.which_epoch)
-    dest = results_dir(opt, known.out, known.use_ema)
+    dest = results_dir(opt, known.out, known.use_ema, known.full_frame)
     os.makedirs(dest, exist_ok=True)
-    dataset = CreateDataLoader(opt, "test", local=True).load_data()
+    if known.full_frame:
+        from data.frame_dataset import frame_loader
+        dataset = frame_loader(opt)
+    else:
+        dataset = CreateDataLoader(opt, "test", local=True).load_data()
     how_many = min(int(opt.how_many), len(dataset))
     print("#test images = %d" % how_many)
     model = create_model(opt)
@@ -164,7 +223,12 @@ def main(argv=None):
             # (zlib level 1: the encoder on the host, not the device, bounds a run that writes panels)
             Image.fromarray(arr).save(os.path.join(dest, p + ".png"), compress_level=1)
 
-    n = run_pass(model.netG, dataset, opt.which_direction == "AtoB", how_many, metrics, on_batch)
+    if known.full_frame:
+        n = run_full_frame_pass(model.netG, dataset, (opt.fineSize_h, opt.fineSize_w), overlap, opt.batchSize,
+                                opt.input_nc == 1, opt.output_nc == 1, opt.which_direction == "AtoB", how_many, metrics,
+                                on_batch)
+    else:
+        n = run_pass(model.netG, dataset, opt.which_direction == "AtoB", how_many, metrics, on_batch)
     if metrics.n == 0:   # --dataset_mode single: no labels, nothing to score
         print("%d panels -> %s" % (n, dest))
         return [], None

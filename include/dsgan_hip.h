@@ -672,6 +672,21 @@ long dsgan_ssim_eval_parts(int N, int C, int H, int W);
 int dsgan_ssim_eval(const float* real, const float* fake, float a, float b, int N, int C, int H, int W,
                     const float* win11, float C1, float C2, int nonneg, float* part, float* out,
                     hipStream_t stream);
+/* ---- whole-frame colourisation (tiles.hip): evaluate.py --full_frame / dsgan_hip/tiling.py ----
+ * A frame [H][W] is cut into ny * nx tiles of th x tw, tile t = iy * nx + ix with its corner at
+ * (oy[iy], ox[ix]); oy (ny ints) and ox (nx ints) are DEVICE arrays, ascending, every tile inside the
+ * frame (the kernels clamp what they read to [0, size - tile]).  At most 1024 tiles per axis.
+ * u8_tiles: dst fp32 [T][gray ? 1 : 3][th][tw] = tiles t0 .. t0 + T - 1 of the uint8 frame src [H][W][3],
+ *   dsgan_u8_to_image's arithmetic without a flip: bit-exact with it on host crops of the same windows.
+ * tiles_blend: out fp32 [C][H][W] from tiles fp32 [ny * nx][C][th][tw], C in {1, 3}, 0 <= overlap <=
+ *   min(th, tw) / 2.  Per pixel and channel num = sum fl(w * v) and den = sum w over the tiles that cover it,
+ *   iy ascending then ix ascending, in fp32 without contraction, out = num / den; w = w1(y - oy) * w1(x - ox)
+ *   with w1(i) = min(i + 1, L - i, overlap) over a tile side L (1 with overlap 0).  A pixel that exactly one
+ *   tile covers is that tile's value, copied.  No atomics: identical calls give identical bits. */
+int dsgan_u8_tiles(const unsigned char* src, int H, int W, const int* oy, int ny, const int* ox, int nx, int th,
+                   int tw, int t0, int T, int gray, float* dst, hipStream_t stream);
+int dsgan_tiles_blend(const float* tiles, int C, int th, int tw, const int* oy, int ny, const int* ox, int nx,
+                      int overlap, int H, int W, float* out, hipStream_t stream);
 /* MS-SSIM evaluation of (a*real+b, a*fake+b), DSGAN/MS_SSIM.py:153-225 (ms_ssim, forward only;
  * the differentiable form is dsgan_ms_ssim_fwd_train + dsgan_ms_ssim_bwd below): per scale the SSIM / contrast-structure plane means, then the padded 2x2 average pool;
  * weights_host = the level weights (host array, levels <= 8).  work: dsgan_ms_ssim_workspace
