@@ -30,6 +30,31 @@ def to_images(u8, flip, gray=False):
     return out
 
 
+def resize_to_images(frames, h_off, w_off, flip, opt, gray=False):
+    """--load_resize: uint8 [N][Hs][Ws][3] whole frames -> fp32 [N][3|1][fineSize_h][fineSize_w] on the GPU, each
+    frame resized to loadSize as ``PIL.Image.resize`` does it, cropped at (h_off[n], w_off[n]), then as
+    ``to_images`` (one device call, dsgan_hip/resample.py)."""
+    from dsgan_hip.resample import resize_crop_to_image
+    offsets = list(zip(torch.as_tensor(h_off).tolist(), torch.as_tensor(w_off).tolist()))
+    return resize_crop_to_image(frames, opt.loadSize_h, opt.loadSize_w, offsets, torch.as_tensor(flip).tolist(),
+                                opt.fineSize_h, opt.fineSize_w, gray, opt.load_resize)
+
+
+def collate_frames(items):
+    """The DataLoader's collate_fn under --load_resize: whole frames stack only when every item of the batch has
+    the same size on a side (A and B may differ from each other); otherwise name two files that differ."""
+    for key, paths in (("A_frame", "A_paths"), ("B_frame", "B_paths")):
+        if key not in items[0]:
+            continue
+        for it in items[1:]:
+            if it[key].shape != items[0][key].shape:
+                raise ValueError("--load_resize: the frames of one batch must share a size, but %s is %dx%d and %s is "
+                                 "%dx%d (h x w); use --batchSize 1 or a dataset of one frame size per side"
+                                 % (items[0][paths], items[0][key].shape[0], items[0][key].shape[1],
+                                    it[paths], it[key].shape[0], it[key].shape[1]))
+    return torch.utils.data.default_collate(items)
+
+
 def _dist():
     if dist.is_available() and dist.is_initialized():
         return dist.get_rank(), dist.get_world_size()
@@ -122,10 +147,13 @@ class CustomDatasetDataLoader:
         # local: this process walks the whole dataset whatever the process group (the evaluation pass)
         rank, world = (0, 1) if local else _dist()
         self.batch_sampler = None
+        # --load_resize: items are whole frames (resized and cropped on the device, __iter__ below)
+        self.load_resize = getattr(opt, "load_resize", "none") != "none"
+        collate = collate_frames if self.load_resize else None
         if world == 1:
             self.dataloader = torch.utils.data.DataLoader(
                 self.dataset, batch_size=opt.batchSize, shuffle=shuffle,
-                num_workers=int(opt.nThreads), pin_memory=True)
+                num_workers=int(opt.nThreads), pin_memory=True, collate_fn=collate)
         else:
             # the same sampler (hence the same RNG draws) as the 1-process loader above
             sampler = (torch.utils.data.RandomSampler(self.dataset) if shuffle
@@ -133,7 +161,7 @@ class CustomDatasetDataLoader:
             self.batch_sampler = RankBatchSampler(sampler, opt.batchSize, rank, world)
             self.dataloader = torch.utils.data.DataLoader(
                 self.dataset, batch_sampler=self.batch_sampler, num_workers=int(opt.nThreads),
-                pin_memory=True)
+                pin_memory=True, collate_fn=collate)
 
     def load_data(self):
         return self
@@ -149,6 +177,14 @@ class CustomDatasetDataLoader:
             if i * opt.batchSize >= opt.max_dataset_size:
                 break
             gb = self.batch_sampler.sizes.popleft() if self.batch_sampler is not None else len(data["A_paths"])
+            if self.load_resize:
+                def img(side, gray):
+                    return resize_to_images(data[side + "_frame"], data["h_off"], data["w_off"], data["flip"], opt, gray)
+                out = {"A": img("A", in_nc == 1), "A_paths": data["A_paths"], "global_batch": gb}
+                if "B_frame" in data:
+                    out["B"], out["B_paths"] = img("B", out_nc == 1), data["B_paths"]
+                yield out
+                continue
             if "B_u8" not in data:     # single dataset (--model test): A only
                 yield {"A": to_images(data["A_u8"], data["flip"], in_nc == 1), "A_paths": data["A_paths"],
                        "global_batch": gb}

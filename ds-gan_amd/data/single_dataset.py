@@ -8,6 +8,9 @@ serves what the class evidently intends -- the A (TIR) half of ``dataroot``, sor
 the same uint8 upload + ``dsgan_u8_to_image`` kernel as the aligned dataset, cropped to
 ``fineSize_h x fineSize_w`` at python-``random`` offsets and never flipped (``isTrain`` is False
 at test time, DSGAN/data/base_dataset.py:33); RGB -> gray when ``input_nc == 1`` (:25-27).
+
+With ``--load_resize bicubic|bilinear`` an item is the whole decoded frame plus offsets drawn over
+``loadSize - fineSize``; the loader resizes it to loadSize and crops it on the device (aligned_dataset.py).
 """
 import os
 import random
@@ -25,12 +28,22 @@ class SingleDataset(torch.utils.data.Dataset):
         self.root = opt.dataroot
         self.dir_A = os.path.join(opt.dataroot)
         self.A_paths = sorted(make_dataset(self.dir_A)[0])
+        self.load_resize = getattr(opt, "load_resize", "none")
+        if self.load_resize != "none":
+            from dsgan_hip.resample import check_geometry
+            check_geometry(opt.loadSize_h, opt.loadSize_w, opt.fineSize_h, opt.fineSize_w)
 
     def __getitem__(self, index):
         opt = self.opt
         A_path = self.A_paths[index]
-        img = np.asarray(Image.open(A_path).convert("RGB"), dtype=np.uint8)
         fh, fw = opt.fineSize_h, opt.fineSize_w
+        if self.load_resize != "none":   # the whole frame; the crop is taken from the resized image on the device
+            img = np.array(Image.open(A_path).convert("RGB"), dtype=np.uint8)
+            w_offset = random.randint(0, opt.loadSize_w - fw)
+            h_offset = random.randint(0, opt.loadSize_h - fh)
+            return {"A_frame": torch.from_numpy(img), "h_off": h_offset, "w_off": w_offset, "flip": 0,
+                    "A_paths": A_path}
+        img = np.asarray(Image.open(A_path).convert("RGB"), dtype=np.uint8)
         w_offset = random.randint(0, max(0, img.shape[1] - fw))
         h_offset = random.randint(0, max(0, img.shape[0] - fh))
         crop = img[h_offset:h_offset + fh, w_offset:w_offset + fw].copy()

@@ -180,6 +180,8 @@ SIGNATURES = {
     # tiles.hip
     "dsgan_u8_tiles": [P, I, I, P, I, P, I, I, I, I, I, I, P, S],
     "dsgan_tiles_blend": [P, I, I, I, P, I, P, I, I, I, I, P, S],
+    # resample.hip
+    "dsgan_u8_resize_crop_to_image": [P, I, I, I, P, P, I, P, P, I, I, I, P, P, I, I, I, P, L, P, S],
     # lsgan.hip
     "dsgan_sigmoid_fwd": [P, L, P, S],
     "dsgan_sigmoid_bwd": [P, P, L, P, I, S],

@@ -66,6 +66,10 @@ def check_options(opt, tile_overlap=None):
     if tile_overlap is not None:
         from dsgan_hip.tiling import check_overlap
         check_overlap(tile_overlap, opt.fineSize_h, opt.fineSize_w)
+        if getattr(opt, "load_resize", "none") != "none":
+            raise ValueError("--full_frame tiles the frame as decoded: --load_resize %s (a resize to loadSize %dx%d "
+                             "before a fineSize crop) does not apply to it; use --load_resize none"
+                             % (opt.load_resize, opt.loadSize_h, opt.loadSize_w))
     if float(opt.aspect_ratio) != 1.0:
         raise ValueError("evaluate.py writes the generator's pixels: --aspect_ratio %s (the reference visualiser's "
                          "resize) is not supported, only 1.0" % opt.aspect_ratio)

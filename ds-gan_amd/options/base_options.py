@@ -1,8 +1,9 @@
 """Command-line options (DSGAN/options/base_options.py:8-141) -- same flag names, defaults and
-``parse(dataset_path, path)`` signature, plus two build flags:
+``parse(dataset_path, path)`` signature, plus three build flags:
 
   --precision {fp32,bf16}   MFMA operand precision of the HIP contractions (fp32 = parity mode)
   --vgg_weights PATH        local VGG16 weights (the reference downloads ImageNet weights)
+  --load_resize {none,bicubic,bilinear}   scale to loadSize on the GPU before the crop, as PIL.Image.resize
 
 The untyped loss-weight flags of the reference (quirk q1: ``--w_gan 0.1`` on the CLI becomes a
 str and crashes the reference) are kept as declared; the model casts them to numbers.
@@ -77,6 +78,10 @@ class BaseOptions:
                             help="operand precision of the MFMA contractions (accumulation is fp32)")
         parser.add_argument("--vgg_weights", type=str, default="",
                             help="local VGG16 weights (torchvision features.* or Vgg16 state dict)")
+        # build extension: resize every decoded image to loadSize_h x loadSize_w on the device, exactly as
+        # PIL.Image.resize with that filter, before the fineSize crop (none: images are cropped as decoded)
+        parser.add_argument("--load_resize", type=str, default="none", choices=["none", "bicubic", "bilinear"],
+                            help="scale images to loadSize on the GPU before the crop (PIL-exact)")
         self.initialized = True
         return parser
 

@@ -687,6 +687,21 @@ int dsgan_u8_tiles(const unsigned char* src, int H, int W, const int* oy, int ny
                    int tw, int t0, int T, int gray, float* dst, hipStream_t stream);
 int dsgan_tiles_blend(const float* tiles, int C, int th, int tw, const int* oy, int ny, const int* ox, int nx,
                       int overlap, int H, int W, float* out, hipStream_t stream);
+/* ---- load-time resize (resample.hip): --load_resize / dsgan_hip/resample.py ----
+ * dst fp32 [N][gray ? 1 : 3][fh][fw] from src uint8 [N][Hs][Ws][3]: every frame resized to load_h x load_w
+ * exactly as PIL.Image.resize does it on 8-bit images (Pillow's Resample.c: per axis and output index a window
+ * (xmin, n) and n 22-bit fixed-point coefficients, a pass = clip8((2^21 + sum p * k) >> 22) in int32, the
+ * horizontal pass first into uint8, then the vertical one), cropped at off[n] = (h_off, w_off), then
+ * dsgan_u8_to_image's arithmetic with flip[n] and `gray`: bit-exact with PIL resize -> host crop ->
+ * dsgan_u8_to_image.  ybounds [load_h][2] / ycoef [load_h][ky] and xbounds [load_w][2] / xcoef [load_w][kx]
+ * are DEVICE int arrays (resample.pil_coeffs), off [N][2] and flip [N] too; ky == 0 (kx == 0): that axis
+ * keeps its size (Hs == load_h, Ws == load_w), its tables are not read and its pass is skipped; ky, kx <= 65.
+ * The kernels clamp every offset and window they read, so no content of those arrays takes an access out
+ * of bounds.  tmp: the horizontal pass's intermediate, N * Hs * fw * 3 bytes when kx > 0 (else unused). */
+int dsgan_u8_resize_crop_to_image(const unsigned char* src, int N, int Hs, int Ws, const int* ybounds,
+                                  const int* ycoef, int ky, const int* xbounds, const int* xcoef, int kx, int load_h,
+                                  int load_w, const int* off, const int* flip, int fh, int fw, int gray,
+                                  unsigned char* tmp, long tmp_bytes, float* dst, hipStream_t stream);
 /* MS-SSIM evaluation of (a*real+b, a*fake+b), DSGAN/MS_SSIM.py:153-225 (ms_ssim, forward only;
  * the differentiable form is dsgan_ms_ssim_fwd_train + dsgan_ms_ssim_bwd below): per scale the SSIM / contrast-structure plane means, then the padded 2x2 average pool;
  * weights_host = the level weights (host array, levels <= 8).  work: dsgan_ms_ssim_workspace
