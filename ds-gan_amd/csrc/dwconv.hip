@@ -527,13 +527,18 @@ static long dw_wgrad_v2_plan(int N, int C, int H, int W, int* nsplit_out, int* n
   return (long)tw * th * nsplit;
 }
 
+// What a tiled weight-grad launch does (dsgan_dwconv_plan reports it): filled in by the launch
+// chain itself, which launches nothing without a workspace.
+struct DwPlanOut { int nsplit, nper, prefetch; };
+
 template <int K, int TWT, int THT, int R, bool PF = false>
 static long dw_wgrad_v2(const float* dy, long dy_bs, const float* x, long x_bs, float* ws, int N, int C, int H, int W,
-                        hipStream_t st) {
+                        hipStream_t st, DwPlanOut* po = nullptr) {
   using T = DwTile<K, TWT, THT, R>;
   const int tw = W / T::TW, th = (H + T::TH - 1) / T::TH;
   int nsplit, nper;
   const long G = dw_wgrad_v2_plan<K, TWT, THT, R>(N, C, H, W, &nsplit, &nper);
+  if (po) *po = DwPlanOut{nsplit, nper, PF ? 1 : 0};
   if (ws)
     hipLaunchKernelGGL((dwconv_wgrad_v2<K, TWT, THT, R, PF>), dim3(tw * th * C * nsplit), dim3(256), 0, st, dy, dy_bs, x,
                        x_bs, ws, N, C, H, W, tw, nper, tw * th);
@@ -559,33 +564,33 @@ static void dw_fwd_dispatch(int cfg, const float* x, long x_bs, const float* w, 
 constexpr int DW_PF_MIN_IMAGES = 8;
 template <int K, int TWT, int THT, int R, int RPF>
 static long dw_wgrad_pick(const float* dy, long dy_bs, const float* x, long x_bs, float* ws, int N, int C, int H,
-                          int W, hipStream_t st) {
+                          int W, hipStream_t st, DwPlanOut* po) {
   int nsplit, nper;
   dw_wgrad_v2_plan<K, TWT, THT, RPF>(N, C, H, W, &nsplit, &nper);
-  if (nper >= DW_PF_MIN_IMAGES) return dw_wgrad_v2<K, TWT, THT, RPF, true>(dy, dy_bs, x, x_bs, ws, N, C, H, W, st);
-  return dw_wgrad_v2<K, TWT, THT, R>(dy, dy_bs, x, x_bs, ws, N, C, H, W, st);
+  if (nper >= DW_PF_MIN_IMAGES) return dw_wgrad_v2<K, TWT, THT, RPF, true>(dy, dy_bs, x, x_bs, ws, N, C, H, W, st, po);
+  return dw_wgrad_v2<K, TWT, THT, R>(dy, dy_bs, x, x_bs, ws, N, C, H, W, st, po);
 }
 template <int K>
 static long dw_wgrad_dispatch(int cfg, const float* dy, long dy_bs, const float* x, long x_bs, float* ws,
-                              int N, int C, int H, int W, hipStream_t st) {
+                              int N, int C, int H, int W, hipStream_t st, DwPlanOut* po) {
   constexpr int R1 = K >= 9 ? 2 : 8, R2 = K >= 9 ? 2 : 4;
   if constexpr (K == 7) {
-    if (cfg == 1) return dw_wgrad_pick<7, 32, 8, R1, 4>(dy, dy_bs, x, x_bs, ws, N, C, H, W, st);
-    if (cfg == 2) return dw_wgrad_pick<7, 16, 16, R2, R2>(dy, dy_bs, x, x_bs, ws, N, C, H, W, st);
-    return dw_wgrad_pick<7, 8, 32, 1, 1>(dy, dy_bs, x, x_bs, ws, N, C, H, W, st);
+    if (cfg == 1) return dw_wgrad_pick<7, 32, 8, R1, 4>(dy, dy_bs, x, x_bs, ws, N, C, H, W, st, po);
+    if (cfg == 2) return dw_wgrad_pick<7, 16, 16, R2, R2>(dy, dy_bs, x, x_bs, ws, N, C, H, W, st, po);
+    return dw_wgrad_pick<7, 8, 32, 1, 1>(dy, dy_bs, x, x_bs, ws, N, C, H, W, st, po);
   }
-  if (cfg == 1) return dw_wgrad_v2<K, 32, 8, R1>(dy, dy_bs, x, x_bs, ws, N, C, H, W, st);
-  if (cfg == 2) return dw_wgrad_v2<K, 16, 16, R2>(dy, dy_bs, x, x_bs, ws, N, C, H, W, st);
-  return dw_wgrad_v2<K, 8, 32, 1>(dy, dy_bs, x, x_bs, ws, N, C, H, W, st);
+  if (cfg == 1) return dw_wgrad_v2<K, 32, 8, R1>(dy, dy_bs, x, x_bs, ws, N, C, H, W, st, po);
+  if (cfg == 2) return dw_wgrad_v2<K, 16, 16, R2>(dy, dy_bs, x, x_bs, ws, N, C, H, W, st, po);
+  return dw_wgrad_v2<K, 8, 32, 1>(dy, dy_bs, x, x_bs, ws, N, C, H, W, st, po);
 }
 
 static long dw_wgrad_any(int K, int cfg, const float* dy, long dy_bs, const float* x, long x_bs, float* ws, int N,
-                         int C, int H, int W, hipStream_t st) {
+                         int C, int H, int W, hipStream_t st, DwPlanOut* po = nullptr) {
   switch (K) {
-    case 3: return dw_wgrad_dispatch<3>(cfg, dy, dy_bs, x, x_bs, ws, N, C, H, W, st);
-    case 5: return dw_wgrad_dispatch<5>(cfg, dy, dy_bs, x, x_bs, ws, N, C, H, W, st);
-    case 7: return dw_wgrad_dispatch<7>(cfg, dy, dy_bs, x, x_bs, ws, N, C, H, W, st);
-    default: return dw_wgrad_dispatch<9>(cfg, dy, dy_bs, x, x_bs, ws, N, C, H, W, st);
+    case 3: return dw_wgrad_dispatch<3>(cfg, dy, dy_bs, x, x_bs, ws, N, C, H, W, st, po);
+    case 5: return dw_wgrad_dispatch<5>(cfg, dy, dy_bs, x, x_bs, ws, N, C, H, W, st, po);
+    case 7: return dw_wgrad_dispatch<7>(cfg, dy, dy_bs, x, x_bs, ws, N, C, H, W, st, po);
+    default: return dw_wgrad_dispatch<9>(cfg, dy, dy_bs, x, x_bs, ws, N, C, H, W, st, po);
   }
 }
 
@@ -600,9 +605,12 @@ static int dw_generic_groups(int N, int C, int H, int W, int* tpb_out) {
   return (ntiles + tpb - 1) / tpb;
 }
 
-static bool dw_tiled_ok(int K, int cfg, const void* x, const void* dy, long x_bs, long dy_bs) {
-  return cfg && K >= 3 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)dy & 15) == 0 && (x_bs & 3) == 0 && (dy_bs & 3) == 0;
+static bool dw_al16(const void* x, const void* y, long x_bs, long y_bs) {
+  return ((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0 && (x_bs & 3) == 0 && (y_bs & 3) == 0;
 }
+// the tile configuration a call takes (0: the generic kernels): dw_cfg's, given K >= 3 and 16-byte
+// aligned operands with batch strides % 4 == 0 -- asked by every entry point and by dsgan_dwconv_plan
+static int dw_call_cfg(int H, int W, int K, bool aligned16) { return K >= 3 && aligned16 ? dw_cfg(H, W) : 0; }
 
 // MidMLKA quarters: one tile configuration for all four kernel sizes (rows per thread safe for
 // 9x9: cfg 1 -> 32 x 8 threads x 2 rows, cfg 2 -> 16 x 16 x 2, cfg 3 -> 8 x 32 x 1)
@@ -617,15 +625,17 @@ static void dw_multi_fwd_launch(const float* x, long x_bs, const DwQuad& q4, flo
 
 template <int TWT, int THT, int R>
 static long dw_multi_wgrad_run(const float* dy, long dy_bs, const float* x, long x_bs, const DwQuad* q4, int N, int q,
-                               int H, int W, hipStream_t st) {
+                               int H, int W, hipStream_t st, DwPlanOut* po) {
   using T = DwTile<9, TWT, THT, R>;
   const int tw = W / T::TW, th = (H + T::TH - 1) / T::TH;
   int nsplit, nper;
   const long G = dw_wgrad_v2_plan<9, TWT, THT, R>(N, q, H, W, &nsplit, &nper, 256);
+  // (the next-image prefetch where a workgroup walks >= 8 images: 101 -> 98 us at C = 128 @ 128^2,
+  // profiles/r04/dw_micro_multi_pf.txt; shorter loops lose 2-6 % to the lower occupancy)
+  const bool pf = nper >= DW_PF_MIN_IMAGES;
+  if (po) *po = DwPlanOut{nsplit, nper, pf ? 1 : 0};
   if (q4) {
-    // (the next-image prefetch where a workgroup walks >= 8 images: 101 -> 98 us at C = 128 @ 128^2,
-    // profiles/r04/dw_micro_multi_pf.txt; shorter loops lose 2-6 % to the lower occupancy)
-    if (nper >= DW_PF_MIN_IMAGES)
+    if (pf)
       hipLaunchKernelGGL((dwconv_multi_wgrad<TWT, THT, R, true>), dim3(tw * th, q, 4 * nsplit), dim3(256), 0, st, dy,
                          dy_bs, x, x_bs, *q4, N, q, H, W, tw, nper, nsplit);
     else
@@ -636,10 +646,10 @@ static long dw_multi_wgrad_run(const float* dy, long dy_bs, const float* x, long
 }
 
 static long dw_multi_wgrad_any(int cfg, const float* dy, long dy_bs, const float* x, long x_bs, const DwQuad* q4,
-                               int N, int q, int H, int W, hipStream_t st) {
-  if (cfg == 1) return dw_multi_wgrad_run<32, 8, 2>(dy, dy_bs, x, x_bs, q4, N, q, H, W, st);
-  if (cfg == 2) return dw_multi_wgrad_run<16, 16, 2>(dy, dy_bs, x, x_bs, q4, N, q, H, W, st);
-  return dw_multi_wgrad_run<8, 32, 1>(dy, dy_bs, x, x_bs, q4, N, q, H, W, st);
+                               int N, int q, int H, int W, hipStream_t st, DwPlanOut* po = nullptr) {
+  if (cfg == 1) return dw_multi_wgrad_run<32, 8, 2>(dy, dy_bs, x, x_bs, q4, N, q, H, W, st, po);
+  if (cfg == 2) return dw_multi_wgrad_run<16, 16, 2>(dy, dy_bs, x, x_bs, q4, N, q, H, W, st, po);
+  return dw_multi_wgrad_run<8, 32, 1>(dy, dy_bs, x, x_bs, q4, N, q, H, W, st, po);
 }
 
 }  // namespace dsg
@@ -652,8 +662,34 @@ extern "C" {
 // pass.  Supported when every quarter takes a tiled configuration: W % 4 == 0, W in {32, 64,
 // multiples of 128}, 16-byte aligned x / y (dy) with batch strides % 4 == 0.
 int dsgan_dwconv_multi_supported(int H, int W, const void* x, long x_bs, const void* y, long y_bs) {
-  return dw_cfg(H, W) != 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0 && (x_bs & 3) == 0 &&
-         (y_bs & 3) == 0;
+  return dw_call_cfg(H, W, 9, dw_al16(x, y, x_bs, y_bs)) != 0;
+}
+
+// The tile configuration a depthwise call takes, on the host (no launch): 0 the generic kernels, 1 the
+// 128 x 64 tiles (W % 128 == 0), 2 the 64 x 64 ones (W = 64), 3 the 32 x 32 ones (W = 32).  aligned16 =
+// both plane operands 16-byte aligned with batch strides % 4 == 0; op = 0 forward / data-grad, 1
+// weight-grad; multi = the four-quarter entry points (C = channels per quarter; 0 there means
+// unsupported).  For a weight-grad *nsplit = workgroups per (channel, tile), *nper = images each
+// walks, *prefetch = the next-image prefetch form runs; with the generic kernel *nsplit = workgroups
+// per plane and *nper = tiles each walks.  -1 for a shape the entry points refuse.
+int dsgan_dwconv_plan(int N, int C, int H, int W, int K, int aligned16, int op, int multi, int* nsplit, int* nper,
+                      int* prefetch) {
+  if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || !(K == 3 || K == 5 || K == 7 || K == 9)) return -1;
+  const int cfg = dw_call_cfg(H, W, multi ? 9 : K, aligned16 != 0);
+  DwPlanOut po{0, 0, 0};
+  if (op == 1) {
+    if (cfg && multi) {
+      dw_multi_wgrad_any(cfg, nullptr, 0, nullptr, 0, nullptr, N, C, H, W, 0, &po);
+    } else if (cfg) {
+      dw_wgrad_any(K, cfg, nullptr, 0, nullptr, 0, nullptr, N, C, H, W, 0, &po);
+    } else if (!multi) {
+      po.nsplit = dw_generic_groups(N, C, H, W, &po.nper);
+    }
+  }
+  if (nsplit) *nsplit = po.nsplit;
+  if (nper) *nper = po.nper;
+  if (prefetch) *prefetch = po.prefetch;
+  return cfg;
 }
 
 // y[:, 4 quarters] (+)= dwconv_{3,5,7,9}(x quarter) + bias (flip = 1, biases NULL: the data-grad)
@@ -666,7 +702,7 @@ int dsgan_dwconv_multi_fwd(const float* x, long x_bs, const float* w3, const flo
   DwQuad q4{};
   q4.w[0] = w3; q4.w[1] = w5; q4.w[2] = w7; q4.w[3] = w9;
   q4.b[0] = b3; q4.b[1] = b5; q4.b[2] = b7; q4.b[3] = b9;
-  const int cfg = dw_cfg(H, W);
+  const int cfg = dw_call_cfg(H, W, 9, dw_al16(x, y, x_bs, y_bs));
   if (cfg == 1) dw_multi_fwd_launch<32, 8, 2>(x, x_bs, q4, y, y_bs, N, q, H, W, flip, accumulate, st);
   else if (cfg == 2) dw_multi_fwd_launch<16, 16, 2>(x, x_bs, q4, y, y_bs, N, q, H, W, flip, accumulate, st);
   else dw_multi_fwd_launch<8, 32, 1>(x, x_bs, q4, y, y_bs, N, q, H, W, flip, accumulate, st);
@@ -676,7 +712,7 @@ int dsgan_dwconv_multi_fwd(const float* x, long x_bs, const float* w3, const flo
 
 // floats of scratch: the four quarters' slot partials, back to back (quarter K uses G*q*(K*K+1))
 long dsgan_dwconv_multi_wgrad_workspace(int N, int q, int H, int W) {
-  const int cfg = dw_cfg(H, W);
+  const int cfg = dw_call_cfg(H, W, 9, true);
   if (!cfg) return 0;
   const long G = dw_multi_wgrad_any(cfg, nullptr, 0, nullptr, 0, nullptr, N, q, H, W, 0);
   return G * q * (10 + 26 + 50 + 82);
@@ -690,7 +726,7 @@ int dsgan_dwconv_multi_wgrad(const float* dy, long dy_bs, const float* x, long x
               "dsgan_dwconv_multi_wgrad: bad args");
   DSG_REQUIRE(dsgan_dwconv_multi_supported(H, W, x, x_bs, dy, dy_bs), "dsgan_dwconv_multi_wgrad: unsupported H=%d W=%d",
               H, W);
-  const int cfg = dw_cfg(H, W);
+  const int cfg = dw_call_cfg(H, W, 9, dw_al16(x, dy, x_bs, dy_bs));
   const long G = dw_multi_wgrad_any(cfg, nullptr, 0, nullptr, 0, nullptr, N, q, H, W, 0);
   DSG_WS(G * q * (10 + 26 + 50 + 82), ws, ws_elems, "dsgan_dwconv_multi_wgrad (dsgan_dwconv_multi_wgrad_workspace)");
   DwQuad q4{};
@@ -719,8 +755,8 @@ int dsgan_dwconv_fwd(const float* x, long x_bs, const float* w, const float* bia
   DSG_REQUIRE(x && w && y && N > 0 && C > 0 && H > 0 && W > 0, "dsgan_dwconv_fwd: bad args");
   DSG_REQUIRE(K == 3 || K == 5 || K == 7 || K == 9, "dsgan_dwconv_fwd: K must be odd and <= 9");
   DSG_REQUIRE((long)N * C <= 65535, "dsgan_dwconv_fwd: N*C > 65535");
-  const int cfg = dw_cfg(H, W);
-  if (cfg && ((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0 && (x_bs & 3) == 0 && (y_bs & 3) == 0) {
+  const int cfg = dw_call_cfg(H, W, K, dw_al16(x, y, x_bs, y_bs));
+  if (cfg) {
     switch (K) {
       case 3: dw_fwd_dispatch<3>(cfg, x, x_bs, w, bias, y, y_bs, N, C, H, W, flip, accumulate, st); break;
       case 5: dw_fwd_dispatch<5>(cfg, x, x_bs, w, bias, y, y_bs, N, C, H, W, flip, accumulate, st); break;
@@ -745,9 +781,9 @@ int dsgan_dwconv_fwd(const float* x, long x_bs, const float* w, const float* bia
 
 // floats of partial-sum scratch dsgan_dwconv_wgrad needs (alignment as the call will see it)
 long dsgan_dwconv_wgrad_workspace(int N, int C, int H, int W, int K, int aligned16) {
-  const int cfg = dw_cfg(H, W);
+  const int cfg = dw_call_cfg(H, W, K, aligned16 != 0);
   long G;
-  if (cfg && K >= 3 && aligned16) {
+  if (cfg) {
     G = dw_wgrad_any(K, cfg, nullptr, 0, nullptr, 0, nullptr, N, C, H, W, 0);
   } else {
     int tpb;
@@ -761,9 +797,9 @@ long dsgan_dwconv_wgrad_workspace(int N, int C, int H, int W, int K, int aligned
 int dsgan_dwconv_wgrad(const float* dy, long dy_bs, const float* x, long x_bs, float* dw, float* db,
                        int N, int C, int H, int W, int K, float* ws, long ws_elems, hipStream_t st) {
   DSG_REQUIRE(dy && x && dw && K >= 1 && K <= DW_MAXK && (K & 1), "dsgan_dwconv_wgrad: bad args");
-  const int cfg = dw_cfg(H, W);
+  const int cfg = dw_call_cfg(H, W, K, dw_al16(x, dy, x_bs, dy_bs));
   long G;
-  const bool tiled = dw_tiled_ok(K, cfg, x, dy, x_bs, dy_bs);
+  const bool tiled = cfg != 0;
   int tpb = 0, groups = 0;
   if (tiled) {
     G = dw_wgrad_any(K, cfg, nullptr, 0, nullptr, 0, nullptr, N, C, H, W, st);   // (plan only)

@@ -188,6 +188,10 @@ __device__ __forceinline__ float2 plane_sum2(float u, float v, float* sh) {
 
 __device__ __forceinline__ float hsum4(float4 v) { return (v.x + v.y) + (v.z + v.w); }
 
+// instnorm_fwd_v4's unguarded case: a plane of exactly C4 <= 4 float4s per thread (the kernel and
+// dsgan_instnorm_plan both ask this)
+__host__ __device__ constexpr bool in_fwd_v4_full(int NT, int C4, int HW4) { return C4 > 0 && C4 <= 4 && HW4 == C4 * NT; }
+
 template <int NT, int C4>
 __global__ __launch_bounds__(NT == 64 ? 256 : NT) void instnorm_fwd_v4(INArgs a) {
   __shared__ float sh[32];
@@ -229,7 +233,7 @@ __global__ __launch_bounds__(NT == 64 ? 256 : NT) void instnorm_fwd_v4(INArgs a)
     // 4K-pixel planes of the 256 x 4 form 45 -> 42 us (1024 @ 32^2: 24 -> 22) on both; with C4 = 16
     // the 16K-pixel planes went 108 -> 113 us on one box and the 64K-pixel ones -4 % on one box,
     // +2.5 % on the other, so those keep the guarded loop.
-    const bool full = C4 <= 4 && HW4 == C4 * NT;
+    const bool full = in_fwd_v4_full(NT, C4, HW4);
     if (full) {
 #pragma unroll
       for (int j = 0; j < C4; ++j) rv[j] = ld(t + j * NT);
@@ -677,35 +681,75 @@ static bool in_bwd_v4_ok(const INBwdArgs& a) {   // (dx is NULL in the 16-bit fo
          (!a.res || al16(a.res, a.res_bs)) && (!a.dres || al16(a.dres, a.dres_bs));
 }
 
-static void in_fwd_v4_launch(const INArgs& a, hipStream_t st) {
-  const int planes = a.N * a.C, HW = a.HW;
-  if (HW <= 64 * 16) hipLaunchKernelGGL((instnorm_fwd_v4<64, 4>), dim3(cdiv(planes, 4)), dim3(256), 0, st, a);
-  else if (HW <= 256 * 16) hipLaunchKernelGGL((instnorm_fwd_v4<256, 4>), dim3(planes), dim3(256), 0, st, a);
-  else if (HW <= 256 * 64) hipLaunchKernelGGL((instnorm_fwd_v4<256, 16>), dim3(planes), dim3(256), 0, st, a);
-  else if (HW <= 1024 * 64) hipLaunchKernelGGL((instnorm_fwd_v4<1024, 16>), dim3(planes), dim3(1024), 0, st, a);
-  else hipLaunchKernelGGL((instnorm_fwd_v4<1024, 0>), dim3(planes), dim3(1024), 0, st, a);
+// The rung of a plane size on the float4 (v4) or the scalar ladder; the scalar ladder has no
+// 256 x 16 rung (its 256-thread form caches 16 scalars per thread).
+enum InRung : int { IN_WAVE = 0, IN_256x4 = 1, IN_256x16 = 2, IN_1024 = 3, IN_STREAM = 4 };
+static int in_rung(int HW, bool v4) {
+  if (HW <= 64 * 16) return IN_WAVE;
+  if (HW <= 256 * 16) return IN_256x4;
+  if (v4) {
+    if (HW <= 256 * 64) return IN_256x16;
+    if (HW <= 1024 * 64) return IN_1024;
+  } else if (HW <= 1024 * 16) {
+    return IN_1024;
+  }
+  return IN_STREAM;
 }
-static void in_fwd_scalar_launch(const INArgs& a, hipStream_t st) {
-  const int planes = a.N * a.C, HW = a.HW;
-  if (HW <= 64 * 16) hipLaunchKernelGGL((instnorm_fwd_kernel<64, 16>), dim3(cdiv(planes, 4)), dim3(256), 0, st, a);
-  else if (HW <= 256 * 16) hipLaunchKernelGGL((instnorm_fwd_kernel<256, 16>), dim3(planes), dim3(256), 0, st, a);
-  else if (HW <= 1024 * 16) hipLaunchKernelGGL((instnorm_fwd_kernel<1024, 16>), dim3(planes), dim3(1024), 0, st, a);
-  else hipLaunchKernelGGL((instnorm_fwd_kernel<1024, 0>), dim3(planes), dim3(1024), 0, st, a);
+
+// What an entry point launches (dsgan_instnorm_plan returns it, the entry points switch on it):
+// bits 0-1 the form (0 scalar, 1 v4, 2 split), bits 2-4 the rung of the one-workgroup forms, bit 5
+// instnorm_fwd_v4's unguarded case, bits 8.. the chunks per plane S of the split forms.
+enum InForm : int { IN_SCALAR = 0, IN_V4 = 1, IN_SPLIT = 2 };
+static int in_plan(long planes, int HW, bool v4_ok, bool bwd, bool ws) {
+  const int S = ws && v4_ok ? in_split_chunks(planes, HW) : 0;
+  if (S) return IN_SPLIT | (S << 8);
+  const int rung = in_rung(HW, v4_ok);
+  if (!v4_ok) return IN_SCALAR | (rung << 2);
+  const int nt = rung == IN_WAVE ? 64 : rung <= IN_256x16 ? 256 : 1024;
+  const int c4 = rung <= IN_256x4 ? 4 : rung == IN_STREAM ? 0 : 16;   // (as in_fwd_v4_launch instantiates)
+  const bool full = !bwd && in_fwd_v4_full(nt, c4, HW >> 2);
+  return IN_V4 | (rung << 2) | (full ? 32 : 0);
 }
-static void in_bwd_v4_launch(const INBwdArgs& a, hipStream_t st) {
-  const int planes = a.N * a.C, HW = a.HW;
-  if (HW <= 64 * 16) in_bwd_launch<64, 4, true>(a, dim3(cdiv(planes, 4)), dim3(256), st);
-  else if (HW <= 256 * 16) in_bwd_launch<256, 4, true>(a, dim3(planes), dim3(256), st);
-  else if (HW <= 256 * 64) in_bwd_launch<256, 16, true>(a, dim3(planes), dim3(256), st);
-  else if (HW <= 1024 * 64) in_bwd_launch<1024, 16, false, IN_BWD_XL>(a, dim3(planes), dim3(1024), st);
-  else hipLaunchKernelGGL((instnorm_bwd_v4<1024, 0, false>), dim3(planes), dim3(1024), 0, st, a);
+static inline int in_plan_form(int plan) { return plan & 3; }
+static inline int in_plan_rung(int plan) { return (plan >> 2) & 7; }
+
+static void in_fwd_v4_launch(const INArgs& a, int rung, hipStream_t st) {
+  const int planes = a.N * a.C;
+  switch (rung) {
+    case IN_WAVE: hipLaunchKernelGGL((instnorm_fwd_v4<64, 4>), dim3(cdiv(planes, 4)), dim3(256), 0, st, a); break;
+    case IN_256x4: hipLaunchKernelGGL((instnorm_fwd_v4<256, 4>), dim3(planes), dim3(256), 0, st, a); break;
+    case IN_256x16: hipLaunchKernelGGL((instnorm_fwd_v4<256, 16>), dim3(planes), dim3(256), 0, st, a); break;
+    case IN_1024: hipLaunchKernelGGL((instnorm_fwd_v4<1024, 16>), dim3(planes), dim3(1024), 0, st, a); break;
+    default: hipLaunchKernelGGL((instnorm_fwd_v4<1024, 0>), dim3(planes), dim3(1024), 0, st, a); break;
+  }
 }
-static void in_bwd_scalar_launch(const INBwdArgs& a, hipStream_t st) {
-  const int planes = a.N * a.C, HW = a.HW;
-  if (HW <= 64 * 16) hipLaunchKernelGGL((instnorm_bwd_kernel<64, 16>), dim3(cdiv(planes, 4)), dim3(256), 0, st, a);
-  else if (HW <= 256 * 16) hipLaunchKernelGGL((instnorm_bwd_kernel<256, 16>), dim3(planes), dim3(256), 0, st, a);
-  else if (HW <= 1024 * 16) hipLaunchKernelGGL((instnorm_bwd_kernel<1024, 16>), dim3(planes), dim3(1024), 0, st, a);
-  else hipLaunchKernelGGL((instnorm_bwd_kernel<1024, 0>), dim3(planes), dim3(1024), 0, st, a);
+static void in_fwd_scalar_launch(const INArgs& a, int rung, hipStream_t st) {
+  const int planes = a.N * a.C;
+  switch (rung) {
+    case IN_WAVE: hipLaunchKernelGGL((instnorm_fwd_kernel<64, 16>), dim3(cdiv(planes, 4)), dim3(256), 0, st, a); break;
+    case IN_256x4: hipLaunchKernelGGL((instnorm_fwd_kernel<256, 16>), dim3(planes), dim3(256), 0, st, a); break;
+    case IN_1024: hipLaunchKernelGGL((instnorm_fwd_kernel<1024, 16>), dim3(planes), dim3(1024), 0, st, a); break;
+    default: hipLaunchKernelGGL((instnorm_fwd_kernel<1024, 0>), dim3(planes), dim3(1024), 0, st, a); break;
+  }
+}
+static void in_bwd_v4_launch(const INBwdArgs& a, int rung, hipStream_t st) {
+  const int planes = a.N * a.C;
+  switch (rung) {
+    case IN_WAVE: in_bwd_launch<64, 4, true>(a, dim3(cdiv(planes, 4)), dim3(256), st); break;
+    case IN_256x4: in_bwd_launch<256, 4, true>(a, dim3(planes), dim3(256), st); break;
+    case IN_256x16: in_bwd_launch<256, 16, true>(a, dim3(planes), dim3(256), st); break;
+    case IN_1024: in_bwd_launch<1024, 16, false, IN_BWD_XL>(a, dim3(planes), dim3(1024), st); break;
+    default: hipLaunchKernelGGL((instnorm_bwd_v4<1024, 0, false>), dim3(planes), dim3(1024), 0, st, a); break;
+  }
+}
+static void in_bwd_scalar_launch(const INBwdArgs& a, int rung, hipStream_t st) {
+  const int planes = a.N * a.C;
+  switch (rung) {
+    case IN_WAVE: hipLaunchKernelGGL((instnorm_bwd_kernel<64, 16>), dim3(cdiv(planes, 4)), dim3(256), 0, st, a); break;
+    case IN_256x4: hipLaunchKernelGGL((instnorm_bwd_kernel<256, 16>), dim3(planes), dim3(256), 0, st, a); break;
+    case IN_1024: hipLaunchKernelGGL((instnorm_bwd_kernel<1024, 16>), dim3(planes), dim3(1024), 0, st, a); break;
+    default: hipLaunchKernelGGL((instnorm_bwd_kernel<1024, 0>), dim3(planes), dim3(1024), 0, st, a); break;
+  }
 }
 
 }  // namespace dsg
@@ -719,10 +763,23 @@ int dsgan_instnorm_fwd(const float* x, long x_bs, const float* scale, const floa
                        float slope, float eps, hipStream_t st) {
   DSG_REQUIRE(x && y && mean && rstd && N > 0 && C > 0 && HW > 0, "dsgan_instnorm_fwd: bad args");
   INArgs a{x, x_bs, scale, res, res_bs, y, y_bs, mean, rstd, N, C, HW, act, slope, eps, 0};
-  if (in_fwd_v4_ok(a)) in_fwd_v4_launch(a, st);
-  else in_fwd_scalar_launch(a, st);
+  const int plan = in_plan((long)N * C, HW, in_fwd_v4_ok(a), false, false);
+  if (in_plan_form(plan) == IN_V4) in_fwd_v4_launch(a, in_plan_rung(plan), st);
+  else in_fwd_scalar_launch(a, in_plan_rung(plan), st);
   DSG_CHECK_LAUNCH();
   return 0;
+}
+
+// The launch form of the InstanceNorm entry points for a shape, on the host (no launch): aligned16 =
+// every plane operand 16-byte aligned with a batch stride % 4 == 0, bwd = a backward entry point, ws =
+// one of the _ws entry points.  Bits 0-1: 0 scalar kernels, 1 float4 kernels, 2 the split forms.
+// Bits 2-4, the rung of the one-workgroup forms: 0 a wave per plane, 1 256 threads (4 float4s or 16
+// scalars each), 2 256 threads x 16 float4s (float4 kernels only), 3 1024 threads cached, 4 1024
+// threads streaming.  Bit 5: the forward float4 kernel's unguarded case (HW = 1024 or 4096).  Bits
+// 8 and up: the chunks per plane of the split forms.  -1 for a shape the entry points refuse.
+int dsgan_instnorm_plan(int N, int C, int HW, int aligned16, int bwd, int ws) {
+  if (N <= 0 || C <= 0 || HW <= 0) return -1;
+  return in_plan((long)N * C, HW, aligned16 && (HW & 3) == 0, bwd != 0, ws != 0);
 }
 
 // Scratch (fp32 elements) of dsgan_instnorm_{fwd,bwd}_ws for this shape: 0 when the one-workgroup-
@@ -740,7 +797,8 @@ int dsgan_instnorm_fwd_ws(const float* x, long x_bs, const float* scale, const f
   DSG_REQUIRE(x && y && mean && rstd && N > 0 && C > 0 && HW > 0, "dsgan_instnorm_fwd_ws: bad args");
   INArgs a{x, x_bs, scale, res, res_bs, y, y_bs, mean, rstd, N, C, HW, act, slope, eps, 0};
   const long planes = (long)N * C;
-  const int S = in_fwd_v4_ok(a) ? in_split_chunks(planes, HW) : 0;
+  const int plan = in_plan(planes, HW, in_fwd_v4_ok(a), false, true);
+  const int S = in_plan_form(plan) == IN_SPLIT ? plan >> 8 : 0;
   DSG_WS(S ? 2 * planes * S : 0, ws, ws_elems, "dsgan_instnorm_fwd_ws");
   if (!S) return dsgan_instnorm_fwd(x, x_bs, scale, res, res_bs, y, y_bs, mean, rstd, N, C, HW, act, slope, eps, st);
   const dim3 g(S, (unsigned)planes);
@@ -760,7 +818,7 @@ int dsgan_instnorm_fwd_bf16(const float* x, long x_bs, void* y, long y_bs, float
   INArgs a{x, x_bs, nullptr, nullptr, 0, (float*)y, y_bs, mean, rstd, N, C, HW, ACT_NONE, 0.f, eps,
            half_type() == HALF_F16 ? 2 : 1};
   DSG_REQUIRE(in_fwd_v4_ok(a), "dsgan_instnorm_fwd_bf16: HW %% 4 and 16-byte alignment");
-  in_fwd_v4_launch(a, st);
+  in_fwd_v4_launch(a, in_plan_rung(in_plan((long)N * C, HW, true, false, false)), st);
   DSG_CHECK_LAUNCH();
   return 0;
 }
@@ -776,7 +834,7 @@ int dsgan_instnorm_bwd_h(const float* dy, long dy_bs, const float* x, long x_bs,
               N, C, HW, act, slope, eps, dxh, dxsum, half_type()};
   DSG_REQUIRE(in_bwd_v4_ok(a) && ((uintptr_t)dxh & 7) == 0 && dxh_bs % 4 == 0,
               "dsgan_instnorm_bwd_h: planes must be float4-aligned (HW %% 4 == 0) and dxh 8-byte aligned");
-  in_bwd_v4_launch(a, st);
+  in_bwd_v4_launch(a, in_plan_rung(in_plan((long)N * C, HW, true, true, false)), st);
   DSG_CHECK_LAUNCH();
   return 0;
 }
@@ -788,8 +846,9 @@ int dsgan_instnorm_bwd(const float* dy, long dy_bs, const float* x, long x_bs, c
   DSG_REQUIRE(dy && x && mean && rstd && dx && N > 0 && C > 0 && HW > 0, "dsgan_instnorm_bwd: bad args");
   INBwdArgs a{dy, dy_bs, x, x_bs, scale, res, res_bs, mean, rstd, dx, dx_bs, dres, dres_bs, dscale,
               N, C, HW, act, slope, eps};
-  if (in_bwd_v4_ok(a)) in_bwd_v4_launch(a, st);
-  else in_bwd_scalar_launch(a, st);
+  const int plan = in_plan((long)N * C, HW, in_bwd_v4_ok(a), true, false);
+  if (in_plan_form(plan) == IN_V4) in_bwd_v4_launch(a, in_plan_rung(plan), st);
+  else in_bwd_scalar_launch(a, in_plan_rung(plan), st);
   DSG_CHECK_LAUNCH();
   return 0;
 }
@@ -803,7 +862,8 @@ int dsgan_instnorm_bwd_ws(const float* dy, long dy_bs, const float* x, long x_bs
   INBwdArgs a{dy, dy_bs, x, x_bs, scale, res, res_bs, mean, rstd, dx, dx_bs, dres, dres_bs, dscale,
               N, C, HW, act, slope, eps};
   const long planes = (long)N * C;
-  const int S = in_bwd_v4_ok(a) ? in_split_chunks(planes, HW) : 0;
+  const int plan = in_plan(planes, HW, in_bwd_v4_ok(a), true, true);
+  const int S = in_plan_form(plan) == IN_SPLIT ? plan >> 8 : 0;
   DSG_WS(S ? 2 * planes * S : 0, ws, ws_elems, "dsgan_instnorm_bwd_ws");
   if (!S)
     return dsgan_instnorm_bwd(dy, dy_bs, x, x_bs, scale, res, res_bs, mean, rstd, dx, dx_bs, dres, dres_bs, dscale,

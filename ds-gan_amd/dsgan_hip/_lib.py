@@ -123,12 +123,14 @@ SIGNATURES = {
     "dsgan_dwconv_multi_fwd": [P, L, P, P, P, P, P, P, P, P, P, L, I, I, I, I, I, I, S],
     "dsgan_dwconv_multi_wgrad_workspace": [I, I, I, I],
     "dsgan_dwconv_multi_wgrad": [P, L, P, L, P, P, P, P, P, P, P, P, I, I, I, I, P, L, S],
+    "dsgan_dwconv_plan": [I, I, I, I, I, I, I, I, P, P, P],
     # instnorm.hip
     "dsgan_instnorm_fwd": [P, L, P, P, L, P, L, P, P, I, I, I, I, F, F, S],
     "dsgan_instnorm_fwd_bf16": [P, L, P, L, P, P, I, I, I, F, S],
     "dsgan_instnorm_bwd": [P, L, P, L, P, P, L, P, P, P, L, P, L, P, I, I, I, I, F, F, S],
     "dsgan_instnorm_bwd_h": [P, L, P, L, P, L, P, P, P, L, P, P, L, I, I, I, I, F, F, S],
     "dsgan_instnorm_workspace": [I, I, I],
+    "dsgan_instnorm_plan": [I, I, I, I, I, I],
     "dsgan_instnorm_fwd_ws": [P, L, P, P, L, P, L, P, P, I, I, I, I, F, F, P, L, S],
     "dsgan_instnorm_bwd_ws": [P, L, P, L, P, P, L, P, P, P, L, P, L, P, I, I, I, I, F, F, P, L, S],
     # maxpool.hip
@@ -227,6 +229,9 @@ SIGNATURES = {
     "dsgan_fingerprint": [P, L, P, L, P, S],
 }
 
+# the plan queries that return int (a code), not the long of the *_workspace / *_plan family
+INT_PLANS = ("dsgan_instnorm_plan", "dsgan_dwconv_plan")
+
 _lib = None
 
 
@@ -244,6 +249,7 @@ def load():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = (ctypes.c_char_p if name == "dsgan_last_error_string"
+                      else ctypes.c_int if name in INT_PLANS
                       else ctypes.c_long if name.endswith(("_workspace", "_parts", "_size", "_need", "_plan")) else ctypes.c_int)
     _lib = lib
     return lib

@@ -432,6 +432,16 @@ int dsgan_dwconv_multi_wgrad(const float* dy, long dy_bs, const float* x, long x
 int dsgan_dwconv_wgrad(const float* dy, long dy_bs, const float* x, long x_bs, float* dw,
                        float* db, int N, int C, int H, int W, int K, float* ws, long ws_elems,
                        hipStream_t stream);
+/* The tile configuration a depthwise call takes, on the host (no launch): 0 the generic kernels, 1 the
+ * 128 x 64 tiles (W % 128 == 0), 2 the 64 x 64 ones (W = 64), 3 the 32 x 32 ones (W = 32); -1 for a
+ * shape the entry points refuse.  aligned16 = both plane operands 16-byte aligned with batch strides
+ * % 4 == 0; op = 0 forward / data-grad, 1 weight-grad; multi = the four-quarter entry points (C =
+ * channels per quarter; 0 there means unsupported).  For a weight-grad *nsplit = workgroups per
+ * (channel, tile), *nper = images each walks, *prefetch = the next-image prefetch form runs; with the
+ * generic kernel *nsplit = workgroups per plane and *nper = tiles each walks.  The launchers take
+ * their decisions from the same functions. */
+int dsgan_dwconv_plan(int N, int C, int H, int W, int K, int aligned16, int op, int multi, int* nsplit, int* nper,
+                      int* prefetch);
 
 /* ---- InstanceNorm2d(affine=False, eps) fused with per-plane scale, residual and activation
  * (instnorm.hip): nn.InstanceNorm2d at MixConvNeXtML.py:54,80,113-116,151,158,221,
@@ -448,6 +458,15 @@ int dsgan_instnorm_bwd(const float* dy, long dy_bs, const float* x, long x_bs, c
  * workgroups per plane, with the plane statistics summed from per-chunk partials in a fixed order.
  * Other shapes need no scratch and run the kernels above. */
 long dsgan_instnorm_workspace(int N, int C, int HW);
+/* The launch form of the InstanceNorm entry points for a shape, on the host (no launch).  aligned16 =
+ * every plane operand 16-byte aligned with a batch stride % 4 == 0, bwd = a backward entry point, ws =
+ * one of the _ws entry points.  Bits 0-1: 0 scalar kernels, 1 float4 kernels, 2 the split forms.  Bits
+ * 2-4, the rung of the one-workgroup forms: 0 a wave per plane, 1 256 threads (4 float4s or 16 scalars
+ * each), 2 256 threads x 16 float4s (float4 kernels only), 3 1024 threads cached, 4 1024 threads
+ * streaming.  Bit 5: the forward float4 kernel's unguarded case (HW = 1024 or 4096).  Bits 8 and up:
+ * the chunks per plane S of the split forms.  -1 for a shape the entry points refuse.  The entry
+ * points switch on the same function. */
+int dsgan_instnorm_plan(int N, int C, int HW, int aligned16, int bwd, int ws);
 int dsgan_instnorm_fwd_ws(const float* x, long x_bs, const float* scale, const float* res, long res_bs,
                           float* y, long y_bs, float* mean, float* rstd, int N, int C, int HW, int act,
                           float slope, float eps, float* ws, long ws_elems, hipStream_t stream);
