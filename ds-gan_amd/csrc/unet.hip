@@ -4,6 +4,7 @@
 //   tanh (the outermost block's nn.Tanh, :501).
 // fp32 in every precision mode; no atomics, no host synchronisation, no allocation.
 #include "common.h"
+#include "philox.h"
 
 namespace dsg {
 
@@ -101,20 +102,6 @@ __global__ __launch_bounds__(256) void prelu_dalpha_kernel(const float* __restri
 // Philox-4x32-10 (Salmon et al., SC'11).  key = the 64-bit seed, counter = (group index lo, hi, call
 // counter, stream id); the four output words decide the four elements 4g .. 4g+3 of the logical dense
 // [N][E] tensor: element kept iff word >= thresh, thresh = round(p * 2^32).
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0,
-                                              unsigned k1, unsigned (&out)[4]) {
-#pragma unroll
-  for (int i = 0; i < 10; ++i) {
-    const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1;
-    const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
 // used[0] <- counter[0], counter[0] += 1: the forward's draw, kept for its backward.
 __global__ void dropout_advance_kernel(long* counter, long* used) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
@@ -231,7 +218,8 @@ static int dropout_launch(const char* who, const float* x, long x_bs, float* y, 
               "%s: bad args", who);
   DSG_REQUIRE(N == 1 || (y_bs >= E && (!x || x_bs >= E)), "%s: batch stride below C*H*W", who);
   const dim3 grid(row_blocks(E), (unsigned)N);
-  const unsigned k0 = (unsigned)((unsigned long)seed & 0xFFFFFFFFul), k1 = (unsigned)((unsigned long)seed >> 32);
+  const PhiloxKey key = philox_key(seed);
+  const unsigned k0 = key.k0, k1 = key.k1;
   const bool v4 = E % 4 == 0 && x_bs % 4 == 0 && y_bs % 4 == 0 && al16(x) && al16(y);
   if (counter) hipLaunchKernelGGL(dropout_advance_kernel, dim3(1), dim3(64), 0, st, counter, used);
   if (v4)

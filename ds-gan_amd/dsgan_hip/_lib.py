@@ -206,6 +206,11 @@ SIGNATURES = {
     "dsgan_dropout_apply": [P, L, P, L, I, L, L, L, P, L, L, F, S],
     "dsgan_tanh_fwd": [P, L, P, S],
     "dsgan_tanh_bwd": [P, P, L, P, I, S],
+    # diffaug.hip
+    "dsgan_diffaug_workspace": [I, I, I, I],
+    "dsgan_diffaug_fwd": [P, L, P, L, P, L, I, I, I, I, I, I, L, L, P, P, I, P, L, S],
+    "dsgan_diffaug_bwd": [P, L, P, L, I, I, I, I, I, I, L, L, P, I, P, L, S],
+    "dsgan_diffaug_params": [P, I, L, L, L, I, I, S],
     # vggconv.hip
     "dsgan_vconv_supported": [I, I, I, I],
     "dsgan_vconv_tune": [I, I],

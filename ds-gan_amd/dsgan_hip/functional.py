@@ -2960,3 +2960,91 @@ class TanhFn(torch.autograd.Function):
 
 def tanh(x):
     return TanhFn.apply(x)
+
+
+# ------------------------------------------------------------------------------------------
+# Differentiable augmentation of the D input (--diffaug; csrc/diffaug.hip, restated in diffaug.py)
+# ------------------------------------------------------------------------------------------
+
+class DiffAugState:
+    """What fixes the augmentation's draws: the 64-bit ``seed``, the ``stream`` id (the rank is folded
+    into it) and ``counter``, an int64 device tensor of one element that the forward advances by the
+    number of calls it draws -- a captured graph augments afresh on every replay.  Sample i of call k
+    draws Philox-4x32-10(key = seed, counter = (i, 0 / 1, k, stream)): see dsgan_hip.diffaug."""
+    __slots__ = ("seed", "stream", "counter")
+
+    def __init__(self, seed, stream, counter):
+        self.seed, self.stream, self.counter = int(seed) & (2 ** 63 - 1), int(stream), counter
+        if not 0 <= self.stream < 2 ** 32:
+            raise ValueError("DiffAugState: stream id out of range")
+        if counter.dtype != torch.int64 or counter.numel() != 1:
+            raise ValueError("DiffAugState: counter must be an int64 tensor of one element")
+
+
+class DiffAugFn(torch.autograd.Function):
+    """y = augment(cat(a, b)) in one pass over a and b (a None: the image alone).  Linear in b once the
+    parameters are drawn: nothing is saved but the call counter drawn, and the backward regenerates
+    the parameters from it.  The condition ``a`` gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, a, b, bits, state, group, out):
+        ctx.box_b = _box(b)
+        b, bbs = nchw(b)
+        N, Cb, H, W = b.shape
+        Ca, abs_ = 0, 0
+        if a is not None:
+            a, abs_ = nchw(a)
+            if a.shape[0] != N or tuple(a.shape[2:]) != (H, W):
+                raise ValueError("diffaug_cat: %s and %s do not concatenate" % (tuple(a.shape), tuple(b.shape)))
+            Ca = a.shape[1]
+        group = N if group is None else int(group)
+        y = out if out is not None else _empty(N, Ca + Cb, H, W, b)
+        if tuple(y.shape) != (N, Ca + Cb, H, W):
+            raise ValueError("diffaug_cat: out has shape %s" % (tuple(y.shape),))
+        y, ybs = _dense4(y, "diffaug_cat")
+        used = torch.empty(1, device=b.device, dtype=torch.int64)
+        ctx.args = (N, Ca, Cb, H, W, int(bits), state.seed, state.stream, group)
+        with _timed(AUX_TIMER, 0.0, ("diffaug_fwd", N, Ca, Cb, H, W, int(bits)), "diffaug",
+                    2 * _nb(y) + (_nb(b) if bits & 1 else 0.0)):
+            call("dsgan_diffaug_fwd", ptr(a), abs_, ptr(b), bbs, ptr(y), ybs, N, Ca, Cb, H, W, int(bits), state.seed,
+                 state.stream, ptr(state.counter), ptr(used), group,
+                 *wsa(_ws("dsgan_diffaug_workspace", N, Cb, H, W, like=b) if bits & 1 else None), stream())
+        ctx.save_for_backward(used)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        if not ctx.needs_input_grad[1]:
+            return None, None, None, None, None, None
+        (used,) = ctx.saved_tensors
+        N, Ca, Cb, H, W, bits, seed, sid, group = ctx.args
+        dy, dybs = nchw(dy)
+        dx = _empty(N, Cb, H, W, dy)
+        with _timed(AUX_TIMER, 0.0, ("diffaug_bwd", N, Ca, Cb, H, W, bits), "diffaug",
+                    (2 + (bits & 1)) * _nb(dx)):
+            call("dsgan_diffaug_bwd", ptr(dy), dybs, ptr(dx), Cb * H * W, N, Ca, Cb, H, W, bits, seed, sid, ptr(used),
+                 group, *wsa(_ws("dsgan_diffaug_workspace", N, Cb, H, W, like=dy) if bits & 1 else None), stream())
+        return None, _give(ctx.box_b, dx), None, None, None, None
+
+
+def diffaug_cat(a, b, policy, state, group=None, out=None):
+    """The augmented channel concatenation cat(a, b) [N, Ca+Cb, H, W] for the discriminator (``a`` None:
+    ``b`` alone).  ``policy``: a --diffaug string or parse_policy's tuple; ``state``: a DiffAugState.
+    Sample n belongs to call ``counter + n // group`` with index ``n % group`` (group None: N, one call),
+    and the counter advances by ceil(N / group).  ``out``: a per-sample dense destination (e.g. a half
+    of a stacked batch); it may not overlap ``a`` or ``b`` (refused by the library)."""
+    from . import diffaug as _da
+    bits = _da.policy_bits(policy)
+    if bits == 0:
+        raise ValueError("diffaug_cat: empty policy (use cat_channels)")
+    return DiffAugFn.apply(a, b, bits, state, group, out)
+
+
+def diffaug_params(seed, stream_id, call_index, n, H, W, device="cuda"):
+    """The draws the kernels make for samples 0..n-1 of call ``call_index``: diffaug.draw_params' dict,
+    computed on the device (dsgan_diffaug_params)."""
+    from . import diffaug as _da
+    t = torch.empty((int(n), 8), device=device, dtype=torch.float32)
+    call("dsgan_diffaug_params", ptr(t), int(n), int(seed) & (2 ** 63 - 1), int(stream_id), int(call_index), int(H),
+         int(W), stream())
+    return _da.unpack_params(t.cpu().numpy())

@@ -184,7 +184,7 @@ class BaseModel:
                             own[k].copy_(v.to(own[k].device, own[k].dtype))
 
     # ---- resumable training: everything beside the weights (--save_state / --resume) ----
-    RANK_STATE_KEYS = ("version", "epoch", "world_size", "precision", "pool", "dropout", "rng")
+    RANK_STATE_KEYS = ("version", "epoch", "world_size", "precision", "pool", "dropout", "rng", "diffaug")
 
     def train_state_dict(self):
         """What a model needs beside its network files to continue bit for bit (Pix2PixModel)."""
@@ -204,7 +204,8 @@ class BaseModel:
         sd["epoch"] = which_epoch
         r = hdist.rank()
         if r > 0:
-            sd = {k: sd[k] for k in self.RANK_STATE_KEYS}
+            # ("diffaug" is there only with the flag on; every other key must be)
+            sd = {k: sd[k] for k in self.RANK_STATE_KEYS if k != "diffaug" or k in sd}
         os.makedirs(self.save_dir, exist_ok=True)
         path = os.path.join(self.save_dir, train_state_filename(which_epoch, r))
         atomic_save(sd, path)

@@ -46,6 +46,11 @@ Deliberate, documented deviations:
     the network files to continue bit for bit -- Adam's moments and steps (torch.optim.Adam's format), the
     scalers, the ImagePool, the dropout counters, step_calls, the RNGs -- restored in place and checked by
     device-side fingerprints of the flat buffers (dsgan_fingerprint); the reference saves weights only.
+  * --diffaug POLICY ('' : off): Differentiable Augmentation (Zhao et al., NeurIPS 2020) of every batch the
+    discriminator sees -- backward_D's fake batch (after the ImagePool query: the pool keeps un-augmented
+    pairs), its real batch, and backward_G's fake batch, in that order: three calls of one counter-based
+    stream per optimize_parameters.  The op (HF.diffaug_cat) also forms the D input, so it replaces the
+    concatenation's copy; the G step's gradient flows back through it.  The image losses see the plain fake_B.
 """
 import contextlib
 import os
@@ -56,6 +61,7 @@ import torch
 from dsgan_hip import _lib
 from dsgan_hip import functional as HF
 from dsgan_hip import dist as hdist
+from dsgan_hip import diffaug as hdiffaug
 from dsgan_hip.flat import FlatParams, FlatAdam
 from dsgan_hip.amp import LossScaler
 from util.image_pool import ImagePool
@@ -190,6 +196,13 @@ class Pix2PixModel(BaseModel):
             self.d_batch_stats = networks.has_batch_stats(self.netD)
             self.vgg_overlap = VGG_OVERLAP
             self._pre_perc = None
+            # --diffaug: the policy and the one counter-based stream all three D passes draw from (its id is
+            # distinct from every dropout layer's: those count up from rank << 16)
+            self.diffaug_policy = hdiffaug.parse_policy(getattr(opt, "diffaug", ""))
+            self.diffaug = None
+            if self.diffaug_policy:
+                self.diffaug = HF.DiffAugState(POOL_SEED, (r << 16) | 0xFFFF,
+                                               torch.zeros(1, device=self.device, dtype=torch.int64))
 
     def set_input(self, input):
         AtoB = self.opt.which_direction == "AtoB"
@@ -218,7 +231,9 @@ class Pix2PixModel(BaseModel):
         else:
             fake_AB = self.fake_B
         fake_AB = fake_AB.detach()
-        if self.d_batch and not self.d_batch_stats and fake_AB.dim() == 4 and fake_AB.dtype == torch.float32:
+        if self.diffaug is not None:
+            pred_fake, pred_real = self._augmented_d_passes(fake_AB)
+        elif self.d_batch and not self.d_batch_stats and fake_AB.dim() == 4 and fake_AB.dtype == torch.float32:
             # the fake and real passes as ONE batch-2N pass of D (D's ops are per-sample: the same
             # outputs, half the launches); neither half needs an input grad
             N, C, H, W = fake_AB.shape
@@ -251,9 +266,34 @@ class Pix2PixModel(BaseModel):
         with HF.deferred_splits():   # the weight-grads' split reductions: one batched flush at the end
             (loss if self.scaler_D is None else self.scaler_D.scale(loss)).backward()
 
+    def _augmented_d_passes(self, fake_AB):
+        """backward_D's two D passes under --diffaug: call k of the stream augments the fake batch, call
+        k + 1 the real one, each in the pass that forms that D input.  The stacked form has the two calls
+        write the halves of the batch-2N input in place of the flag-off form's copies (no byte moves twice);
+        the draws are those of the two-pass form, so both forms stay the same function."""
+        N, C, H, W = fake_AB.shape
+        Ca = self.real_A.shape[1] if self.use_condition == 1 else 0
+        pol, st = self.diffaug_policy, self.diffaug
+        fake_A, real_A = (fake_AB[:, :Ca], self.real_A) if Ca else (None, None)
+        if self.d_batch and not self.d_batch_stats and fake_AB.dtype == torch.float32:
+            AB = torch.empty((2 * N, C, H, W), device=fake_AB.device, dtype=torch.float32)
+            HF.diffaug_cat(fake_A, fake_AB[:, Ca:], pol, st, out=AB[:N])
+            HF.diffaug_cat(real_A, self.real_B, pol, st, out=AB[N:])
+            pred = self.netD(AB)
+            if isinstance(pred, list):
+                return [[t[:N] for t in s] for s in pred], [[t[N:] for t in s] for s in pred]
+            return pred[:N], pred[N:]
+        pred_fake = self.netD(HF.diffaug_cat(fake_A, fake_AB[:, Ca:], pol, st))
+        pred_real = self.netD(HF.diffaug_cat(real_A, self.real_B, pol, st))
+        return pred_fake, pred_real
+
     def backward_G(self):
         if self.use_gan == 1:
-            fake_AB = HF.cat_channels(self.real_A, self.fake_B) if self.use_condition == 1 else self.fake_B
+            if self.diffaug is not None:
+                fake_AB = HF.diffaug_cat(self.real_A if self.use_condition == 1 else None, self.fake_B,
+                                         self.diffaug_policy, self.diffaug)
+            else:
+                fake_AB = HF.cat_channels(self.real_A, self.fake_B) if self.use_condition == 1 else self.fake_B
             self.loss_G_GAN = self.criterionGAN(self.netD(fake_AB), True)
         else:
             self.loss_G_GAN = 0
@@ -597,6 +637,9 @@ class Pix2PixModel(BaseModel):
                                           ("D", self.netD, self.flatD, self.optimizer_D, self.scaler_D)):
             sd["optimizer_" + key] = dict(optim.state_dict(), param_names=self._param_names(net, flat))
             sd["scaler_" + key] = sc.state_dict() if sc is not None else None
+        if self.diffaug is not None:
+            sd["diffaug"] = {"counter": int(self.diffaug.counter.item()), "seed": int(self.diffaug.seed),
+                             "stream": int(self.diffaug.stream), "policy": ",".join(self.diffaug_policy)}
         return sd
 
     def load_train_state_dict(self, sd, own):
@@ -613,6 +656,11 @@ class Pix2PixModel(BaseModel):
         if sd["precision"] != HF.get_precision():
             raise RuntimeError("the training state was saved with --precision %s, this run uses %s: not resumable"
                                % (sd["precision"], HF.get_precision()))
+        theirs = (own.get("diffaug") or {}).get("policy", "")
+        if theirs != ",".join(self.diffaug_policy):
+            raise RuntimeError("the training state was saved with --diffaug %r, this run uses --diffaug %r: not "
+                               "resumable (the discriminator would see another distribution)"
+                               % (theirs, ",".join(self.diffaug_policy)))
         for key, net, flat, optim, sc in (("G", self.netG, self.flatG, self.optimizer_G, self.scaler_G),
                                           ("D", self.netD, self.flatD, self.optimizer_D, self.scaler_D)):
             if (sd["scaler_" + key] is None) != (sc is None):
@@ -635,6 +683,13 @@ class Pix2PixModel(BaseModel):
             with torch.no_grad():
                 m.drop_counter.fill_(int(d["counter"]))
             m.drop_seed, m.drop_stream = int(d["seed"]), int(d["stream"])
+        if self.diffaug is not None:
+            d = own["diffaug"]
+            if (self.diffaug.seed, self.diffaug.stream) != (int(d["seed"]), int(d["stream"])):
+                self._graphs, self._graph_warm = {}, set()   # kernel arguments of the captured graphs
+            with torch.no_grad():
+                self.diffaug.counter.fill_(int(d["counter"]))
+            self.diffaug.seed, self.diffaug.stream = int(d["seed"]) & (2 ** 63 - 1), int(d["stream"])
         load_rng_state_dict(own["rng"], self.device)
         # verification: the restored buffers (and the weight files loaded beside this state) hash to the file's
         if sd["layout"] != self._layout_signature():

@@ -43,8 +43,21 @@ class TrainOptions(BaseOptions):
         # saved as {epoch}_useSE_net_G_ema.pth beside the raw G, scored by evaluate.py --use_ema
         parser.add_argument("--ema_decay", type=float, default=0.0,
                             help="decay of the generator's weight average, in [0, 1) (0: off; e.g. 0.999)")
+        # build extension: Differentiable Augmentation (Zhao et al., NeurIPS 2020) of every batch the
+        # discriminator sees, real or fake, in one HIP pass that also forms the D input; the generator's
+        # gradient flows back through the same transform.  The remedy for a D that memorises a small set.
+        parser.add_argument("--diffaug", type=_diffaug_policy, default="",
+                            help="augment the discriminator's input: a comma-separated subset of "
+                                 "color,translation,cutout (empty: off)")
         self.isTrain = True
         return parser
+
+
+def _diffaug_policy(s):
+    """--diffaug's value in its canonical spelling; an unknown or repeated name is a ValueError naming it
+    (argparse reports it as a usage error)."""
+    from dsgan_hip.diffaug import policy_string
+    return policy_string(s)
 
 
 def default_train_opt(args=None, **overrides):
@@ -60,4 +73,5 @@ def default_train_opt(args=None, **overrides):
     opt.checkpoints_dir = os.path.join(os.environ.get("TMPDIR", "/tmp"), "dsgan_checkpoints")
     for k, v in overrides.items():
         setattr(opt, k, v)
+    opt.diffaug = _diffaug_policy(opt.diffaug)
     return opt

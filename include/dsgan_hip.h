@@ -659,6 +659,36 @@ int dsgan_dropout_apply(const float* x, long x_bs, float* y, long y_bs, int N, l
                         const long* used, long ctr_val, long thresh, float scale, hipStream_t stream);
 int dsgan_tanh_fwd(const float* x, long n, float* y, hipStream_t stream);
 int dsgan_tanh_bwd(const float* y, const float* dy, long n, float* dx, int accumulate, hipStream_t stream);
+/* ---- differentiable augmentation of the D input (diffaug.hip; --diffaug); fp32 NCHW ----
+ * y [N, Ca+Cb, H, W] = cutout(translation(color(cat(a, b)))): a (NULL with Ca == 0) is the condition,
+ * b the image; each has its own batch stride (an already concatenated tensor passes b = a + Ca*H*W).
+ * policy: bit 0 color, bit 1 translation, bit 2 cutout; an op outside it is the identity.
+ * Sample i of call k draws w = Philox-4x32-10(key = seed, counter = (i, 0, k lo, stream_id)) and
+ * v = ...(i, 1, k lo, stream_id); u24(x) = (x >> 8) 2^-24, mulhi(x, m) = (x m) >> 32:
+ *   color, image channels only: b = u24(w0) - 1/2, s = 2 u24(w1), c = u24(w2) + 1/2; u = x + b,
+ *     u' = (u - mean_c u) s + mean_c u, u'' = (u' - M) c + M with M = the sample's mean of u';
+ *   translation, all channels: tx = mulhi(w3, 2 Sx + 1) - Sx, ty = mulhi(v0, 2 Sy + 1) - Sy,
+ *     Sx = floor(W/8 + 1/2), Sy likewise: y[r, q] = x[r - ty, q - tx], 0 outside;
+ *   cutout, all channels: ch = floor(H/2 + 1/2), oy = mulhi(v1, H + 1 - ch % 2) (cw, ox from v2 likewise):
+ *     rows [oy - ch/2, oy - ch/2 + ch) x the like columns, clipped, are 0.
+ * _fwd: used[0] <- counter[0], counter[0] += ceil(N / group) on the device; sample n belongs to call
+ *   used[0] + n / group with index n % group (one stacked launch draws what several smaller ones draw).
+ * _bwd: dx [N, Cb, H, W] = the transpose applied to the image channels of dy [N, Ca+Cb, H, W], with
+ *   the draws of the forward that left `used`.
+ * The destination may not overlap a source (a shifted row is read after other lanes may have written
+ * it): refused on the host when the two address ranges, batch strides included, intersect.
+ * Both take dsgan_diffaug_workspace(N, Cb, H, W) floats: the block partials of the per-sample mean,
+ * added in a fixed order (no atomics); not touched when color is off.
+ * _params: out [n, 8] <- (b, s, c, tx, ty, oy, ox, 0) of samples 0..n-1 of call `call`: fp32 values
+ *   and int32 bit patterns. */
+long dsgan_diffaug_workspace(int N, int Cb, int H, int W);
+int dsgan_diffaug_fwd(const float* a, long a_bs, const float* b, long b_bs, float* y, long y_bs, int N, int Ca, int Cb,
+                      int H, int W, int policy, long seed, long stream_id, long* counter, long* used, int group,
+                      float* ws, long ws_elems, hipStream_t stream);
+int dsgan_diffaug_bwd(const float* dy, long dy_bs, float* dx, long dx_bs, int N, int Ca, int Cb, int H, int W,
+                      int policy, long seed, long stream_id, const long* used, int group,
+                      float* ws, long ws_elems, hipStream_t stream);
+int dsgan_diffaug_params(float* out, int n, long seed, long stream_id, long call, int H, int W, hipStream_t stream);
 /* input pipeline, DSGAN/data/aligned_dataset.py:38-86 (ToTensor, crop, Normalize(0.5,0.5), flip,
  * optional gray): src uint8 [N][H][W][3] (already cropped), flip int [N] (device), dst fp32
  * [N][3 or 1][H][W]; bit-exact with the reference's torch CPU transforms. */
