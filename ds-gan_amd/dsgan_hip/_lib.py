@@ -211,6 +211,11 @@ SIGNATURES = {
     "dsgan_diffaug_fwd": [P, L, P, L, P, L, I, I, I, I, I, I, L, L, P, P, I, P, L, S],
     "dsgan_diffaug_bwd": [P, L, P, L, I, I, I, I, I, I, L, L, P, I, P, L, S],
     "dsgan_diffaug_params": [P, I, L, L, L, I, I, S],
+    # spectral.hip
+    "dsgan_sn_fields": [],
+    "dsgan_sn_parts": [I, I],
+    "dsgan_sn_refresh": [P, I, I, I, I, S],
+    "dsgan_sn_backward": [P, I, I, I, S],
     # vggconv.hip
     "dsgan_vconv_supported": [I, I, I, I],
     "dsgan_vconv_tune": [I, I],

@@ -3048,3 +3048,66 @@ def diffaug_params(seed, stream_id, call_index, n, H, W, device="cuda"):
     call("dsgan_diffaug_params", ptr(t), int(n), int(seed) & (2 ** 63 - 1), int(stream_id), int(call_index), int(H),
          int(W), stream())
     return _da.unpack_params(t.cpu().numpy())
+
+
+# ------------------------------------------------------------------------------------------
+# Spectral normalisation of the D's conv weights (--spectral_norm; csrc/spectral.hip, restated in spectral.py)
+# ------------------------------------------------------------------------------------------
+
+class SpectralTable:
+    """The device table of dsgan_sn_refresh / dsgan_sn_backward over n layers and the two batched calls.
+    ``layers``: one (W, W_sn, u, v, G, dW) per layer -- the weight [Cout, ...] (viewed [R, C] = [Cout, rest]),
+    the buffer W_sn is written to, the unit vectors u [R] and v [C], the scratch G the weight-grad kernels
+    accumulated into and weight_orig's gradient dW (both None in a table that only refreshes); fp32, dense,
+    on one device.  ``sigma`` [n] (allocated when None) receives the layers' sigma; the temporaries
+    t [C], a [R] and the backward's partial sums live here.  The table holds addresses: it is valid while
+    the tensors are (it keeps them alive) and must be rebuilt when one is replaced."""
+
+    def __init__(self, layers, sigma=None):
+        lib = _lib.load()
+        self.layers = [tuple(l) for l in layers]
+        if not self.layers:
+            raise ValueError("SpectralTable: no layer")
+        dev = self.layers[0][0].device
+        n = len(self.layers)
+        self.sigma = sigma if sigma is not None else torch.zeros(n, device=dev, dtype=torch.float32)
+        if tuple(self.sigma.shape) != (n,):
+            raise ValueError("SpectralTable: sigma must have one element per layer")
+        self.can_backward = all(l[4] is not None and l[5] is not None for l in self.layers)
+        rows, self.tmp, self.shapes = [], [], []
+        for i, (W, Wsn, u, v, G, dW) in enumerate(self.layers):
+            R, C = int(W.shape[0]), int(W[0].numel())
+            want = {"W": (W, R * C), "W_sn": (Wsn, R * C), "u": (u, R), "v": (v, C), "G": (G, R * C), "dW": (dW, R * C),
+                    "sigma": (self.sigma, n)}
+            for name, (t, k) in want.items():
+                if t is None and name in ("G", "dW"):
+                    continue
+                if t is None or t.device != dev or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() \
+                        or t.numel() != k:
+                    raise ValueError("SpectralTable: layer %d: %s must be a dense fp32 tensor of %d elements on %s"
+                                     % (i, name, k, dev))
+            tmp = (torch.zeros(C, device=dev), torch.zeros(R, device=dev),
+                   torch.zeros(lib.dsgan_sn_parts(R, C), device=dev))
+            self.tmp.append(tmp)
+            self.shapes.append((R, C))
+            rows.append([ptr(W), ptr(Wsn), ptr(u), ptr(v), ptr(self.sigma[i:]), ptr(tmp[0]), ptr(tmp[1]), ptr(tmp[2]),
+                         ptr(G) or 0, ptr(dW) or 0, R, C])
+        if len(rows[0]) != lib.dsgan_sn_fields():
+            raise RuntimeError("SpectralTable: the library's table has %d fields" % lib.dsgan_sn_fields())
+        self.max_r, self.max_c = max(r for r, _ in self.shapes), max(c for _, c in self.shapes)
+        self.nbytes = 4.0 * sum(r * c for r, c in self.shapes)
+        self.desc = torch.tensor(rows, dtype=torch.int64).to(dev)
+
+    def refresh(self, iterate=True):
+        """u, v, sigma and W_sn of every layer from its W: one power iteration, or (``iterate`` False) sigma
+        and W_sn again from the stored (u, v).  The caller bumps the weight generation of the W_sn tensors."""
+        with _timed(AUX_TIMER, 0.0, ("sn_refresh", len(self.layers), int(bool(iterate))), "spectral",
+                    (4 if iterate else 3) * self.nbytes):
+            call("dsgan_sn_refresh", ptr(self.desc), len(self.layers), self.max_r, self.max_c, int(bool(iterate)), stream())
+
+    def backward(self):
+        """dW += (G - <G, W_sn> u v^T) / sigma per layer; G is left zeroed."""
+        if not self.can_backward:
+            raise RuntimeError("SpectralTable.backward: the table was built without G / dW")
+        with _timed(AUX_TIMER, 0.0, ("sn_backward", len(self.layers)), "spectral", 6 * self.nbytes):
+            call("dsgan_sn_backward", ptr(self.desc), len(self.layers), self.max_r, self.max_c, stream())

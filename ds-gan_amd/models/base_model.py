@@ -10,6 +10,7 @@ from collections import OrderedDict
 
 import torch
 
+from dsgan_hip import spectral as hspectral
 from . import networks
 
 
@@ -165,6 +166,8 @@ class BaseModel:
                 state_dict = torch.load(path, map_location="cpu", weights_only=True)
                 state_dict = OrderedDict((k[7:] if k.startswith("module.") else k, v) for k, v in state_dict.items())
                 own = net.state_dict()
+                # a plain D file offered to a --spectral_norm run, or the reverse: refused, naming the keys
+                hspectral.check_state_keys(own.keys(), state_dict.keys(), "net%s" % name)
                 # the reference's pre-0.4 InstanceNorm patch (:108-109): running statistics saved for a
                 # layer that tracks none are dropped; a BatchNorm's own buffers load like any key
                 state_dict = {k: v for k, v in state_dict.items()
@@ -182,6 +185,8 @@ class BaseModel:
                     for k, v in state_dict.items():
                         if k in own:
                             own[k].copy_(v.to(own[k].device, own[k].dtype))
+                if getattr(net, "spectral", None) is not None:   # W_sn and sigma of the loaded (W, u, v)
+                    net.spectral.refresh(iterate=False)
 
     # ---- resumable training: everything beside the weights (--save_state / --resume) ----
     RANK_STATE_KEYS = ("version", "epoch", "world_size", "precision", "pool", "dropout", "rng", "diffaug")
@@ -242,3 +247,7 @@ class BaseModel:
             if net is not None:
                 for param in net.parameters():
                     param.requires_grad = requires_grad
+                # --spectral_norm: the convs read the W_sn leaves, which are no parameters; frozen with
+                # the rest, they get no weight-grad launch in the G step
+                for w in networks.spectral_weights(net):
+                    w.requires_grad = requires_grad

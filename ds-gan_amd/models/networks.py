@@ -9,7 +9,9 @@ without the trailing ``nn.Sigmoid`` (``use_sigmoid``).  Both objectives are here
 reference's backwards-wired ``--no_lsgan`` turns ON together with the sigmoid (quirk q3).  ``multi``
 without the sigmoid raises: the reference pairs it with ``BCELoss`` on raw logits, which fails in
 torch itself.  ``--norm batch`` builds the ``basic`` / ``n_layers`` PatchGAN on BatchNorm2d (fused
-BatchNorm + LeakyReLU kernels, HF.batch_norm).  ``define_G`` builds ``MixConvNeXtML`` and the
+BatchNorm + LeakyReLU kernels, HF.batch_norm).  ``define_D(..., spectral_norm=True)`` (--spectral_norm)
+builds any of them as an SN-PatchGAN: spectrally normalised conv holders (``SNConv2d``), no norm layer,
+and a ``SpectralState`` that keeps W_sn current (csrc/spectral.hip).  ``define_G`` builds ``MixConvNeXtML`` and the
 ``unet_128`` U-Net (models/unet.py: PReLU, dropout and tanh on HIP kernels, either norm); the other
 reference generators (``unet_256`` by name, the ResNets, ``gll``, ``cascaded``) are out of scope
  and raise the reference's own error.
@@ -57,14 +59,16 @@ def init_weights(net, init_type="normal", gain=0.02):
     def init_func(m):
         classname = m.__class__.__name__
         if hasattr(m, "weight") and (classname.find("Conv") != -1 or classname.find("Linear") != -1):
+            # (a spectrally normalised holder's parameter is weight_orig; its .weight is derived)
+            w = m.weight_orig if isinstance(m, SNConv2d) else m.weight
             if init_type == "normal":
-                init.normal_(m.weight.data, 0.0, gain)
+                init.normal_(w.data, 0.0, gain)
             elif init_type == "xavier":
-                init.xavier_normal_(m.weight.data, gain=gain)
+                init.xavier_normal_(w.data, gain=gain)
             elif init_type == "kaiming":
-                init.kaiming_normal_(m.weight.data, a=0, mode="fan_in")
+                init.kaiming_normal_(w.data, a=0, mode="fan_in")
             elif init_type == "orthogonal":
-                init.orthogonal_(m.weight.data, gain=gain)
+                init.orthogonal_(w.data, gain=gain)
             else:
                 raise NotImplementedError("initialization method [%s] is not implemented" % init_type)
             if hasattr(m, "bias") and m.bias is not None:
@@ -117,13 +121,21 @@ def define_G(input_nc, output_nc, ngf, which_model_netG, norm="batch", use_dropo
 
 
 def define_D(input_nc, ndf, which_model_netD, n_layers_D=3, norm="batch", use_sigmoid=False,
-             init_type="normal", gpu_ids=()):
+             init_type="normal", gpu_ids=(), spectral_norm=False):
     """DSGAN/models/networks.py:115-131.  The discriminators run InstanceNorm (affine=False, the
     reference default ``--norm instance``) fused into their conv kernels.  ``--norm batch`` (affine
     BatchNorm2d with running statistics, bias-free convs in front of it) is built for the ``basic`` /
     ``n_layers`` PatchGAN on the fused BatchNorm kernels (HF.batch_norm); ``pixel`` / ``multi`` with it,
     and ``none`` (which fails in the reference itself: ``norm_layer`` is None), raise instead of
-    silently training a different discriminator."""
+    silently training a different discriminator.
+
+    ``spectral_norm`` (--spectral_norm, a build extension) builds the SN-PatchGAN form of any of them:
+    every conv a spectrally normalised holder (SNConv2d) with a bias, ``nn.Identity()`` where the norm
+    layer stood (the Sequential indices and the keys do not move) and LeakyReLU in the conv epilogue;
+    ``norm`` is then not looked at (it steers the generator only).  The returned net carries its
+    SpectralState (``net.spectral``), refreshed once."""
+    if spectral_norm:
+        return _define_sn_D(input_nc, ndf, which_model_netD, n_layers_D, use_sigmoid, init_type, gpu_ids)
     if norm == "batch" and which_model_netD in ("pixel", "multi"):
         raise NotImplementedError("define_D: norm [batch] is not supported for the [%s] discriminator on the "
                                   "MI355X build (basic / n_layers only)" % which_model_netD)
@@ -147,6 +159,139 @@ def define_D(input_nc, ndf, which_model_netD, n_layers_D=3, norm="batch", use_si
     else:
         raise NotImplementedError("Discriminator model name [%s] is not recognized" % which_model_netD)
     return init_net(netD, init_type, gpu_ids)
+
+
+def _define_sn_D(input_nc, ndf, which_model_netD, n_layers_D, use_sigmoid, init_type, gpu_ids):
+    if which_model_netD == "basic":
+        netD = NLayerDiscriminator(input_nc, ndf, n_layers=3, norm_layer=None, use_sigmoid=use_sigmoid, spectral_norm=True)
+    elif which_model_netD == "n_layers":
+        netD = NLayerDiscriminator(input_nc, ndf, n_layers_D, norm_layer=None, use_sigmoid=use_sigmoid,
+                                   spectral_norm=True)
+    elif which_model_netD == "pixel":
+        netD = PixelDiscriminator(input_nc, ndf, norm_layer=None, use_sigmoid=use_sigmoid, spectral_norm=True)
+    elif which_model_netD == "multi":
+        if not use_sigmoid:
+            raise NotImplementedError("define_D: [multi] without --no_lsgan is not supported (with or without "
+                                      "--spectral_norm): pass --no_lsgan (sigmoid + least squares)")
+        netD = MultiscaleDiscriminator(input_nc, ndf, n_layers_D, None, use_sigmoid, num_D=3, getIntermFeat=False,
+                                       spectral_norm=True)
+    else:
+        raise NotImplementedError("Discriminator model name [%s] is not recognized" % which_model_netD)
+    netD = init_net(netD, init_type, gpu_ids)
+    netD.spectral = SpectralState(netD)
+    return netD
+
+
+class SNConv2d(nn.Module):
+    """A conv holder whose ``.weight`` is the spectrally normalised W_sn = weight_orig / sigma.  Parameters
+    and buffers carry torch.nn.utils.spectral_norm's names and order (``bias``, ``weight_orig``;
+    ``weight_u``, ``weight_v``), so the state dict loads into the same conv wrapped by torch, and back.
+    ``.weight`` is a plain tensor, not a parameter: a persistent leaf that the net's SpectralState
+    rewrites in place (dsgan_hip.spectral states the function).  ``index``: the layer's number in its
+    discriminator, which seeds the draw of the starting ``u``."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, index=0):
+        super().__init__()
+        from dsgan_hip import spectral as hsn
+        k = int(kernel_size)
+        self.in_channels, self.out_channels = int(in_channels), int(out_channels)
+        self.kernel_size, self.stride, self.padding = (k, k), (int(stride),) * 2, (int(padding),) * 2
+        self.index = int(index)
+        ref = nn.Conv2d(in_channels, out_channels, k, stride, padding)   # the default init, the same RNG draws
+        self.bias = nn.Parameter(ref.bias.detach().clone())
+        self.weight_orig = nn.Parameter(ref.weight.detach().clone())
+        self.register_buffer("weight_u", hsn.initial_u(self.index, out_channels))
+        self.register_buffer("weight_v", torch.zeros(in_channels * k * k))
+        self.weight = None   # set by SpectralState
+
+    def forward(self, x):
+        return nn.functional.conv2d(x, self.weight, self.bias, self.stride, self.padding)
+
+    def extra_repr(self):
+        return "%d, %d, kernel_size=%s, stride=%s, padding=%s, spectral_norm" % (
+            self.in_channels, self.out_channels, self.kernel_size, self.stride, self.padding)
+
+
+def spectral_weights(net):
+    """The W_sn tensors of ``net``'s spectrally normalised convs ([] for a plain net)."""
+    return [m.weight for m in net.modules() if isinstance(m, SNConv2d) and m.weight is not None]
+
+
+class SpectralState:
+    """What --spectral_norm keeps beside a discriminator's parameters, and the two batched calls over its
+    layers (csrc/spectral.hip): ``refresh`` rewrites every layer's u, v, sigma and W_sn from the current
+    ``weight_orig`` (once per weight version: at construction, after every optimizer step, ``iterate=False``
+    after a load), ``backward`` folds the gradients the conv kernels accumulated into the W_sn leaves'
+    ``.grad`` scratch into ``weight_orig.grad`` and leaves the scratch zeroed.
+
+    W_sn, the scratch, sigma and the temporaries are persistent device buffers; the kernels find them
+    through a device table of addresses, rebuilt when a parameter or buffer has moved (FlatParams rebinds
+    the parameters into its flat buffers).  On the CPU (no hot path there: tests, state-dict handling)
+    ``refresh`` runs dsgan_hip.spectral's torch reference and ``backward`` is not available."""
+
+    def __init__(self, net):
+        self.convs = [m for m in net.modules() if isinstance(m, SNConv2d)]
+        if not self.convs:
+            raise ValueError("SpectralState: the net has no spectrally normalised conv")
+        self.device = self.convs[0].weight_orig.device
+        self._bound, self._tab = None, None
+        if self.device.type == "cuda":
+            offs, n = [], 0
+            for c in self.convs:   # every tensor on a 256-byte boundary, as FlatParams lays them
+                offs.append(n)
+                n += (c.weight_orig.numel() + 63) // 64 * 64
+            self.wsn = torch.zeros(n, device=self.device, dtype=torch.float32)
+            self.scratch = torch.zeros(n, device=self.device, dtype=torch.float32)
+            self.sigma = torch.zeros(len(self.convs), device=self.device, dtype=torch.float32)
+            for conv, off in zip(self.convs, offs):
+                k, shape = conv.weight_orig.numel(), conv.weight_orig.shape
+                conv.weight = self.wsn[off:off + k].view(shape).detach().requires_grad_(True)
+                conv.weight.grad = self.scratch[off:off + k].view(shape)
+        else:
+            self.sigma = torch.zeros(len(self.convs))
+        self.weights = None
+        self.refresh(iterate=True)
+        self.weights = [c.weight for c in self.convs]
+        # a state dict loaded through nn.Module.load_state_dict brings its own (u, v): recompute W_sn
+        net.register_load_state_dict_post_hook(lambda module, incompatible: self.refresh(iterate=False))
+
+    def table(self):
+        """The HF.SpectralTable over the layers, rebuilt when a parameter, its gradient or a buffer has moved."""
+        for c in self.convs:
+            if c.weight_orig.grad is None:   # a free-standing net: FlatParams binds .grad up front
+                c.weight_orig.grad = torch.zeros_like(c.weight_orig)
+        bound = tuple(t.data_ptr() for c in self.convs for t in (c.weight_orig, c.weight_orig.grad, c.weight_u, c.weight_v))
+        if bound != self._bound:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("SpectralState: a parameter moved during a HIP graph capture")
+            self._tab = HF.SpectralTable([(c.weight_orig.detach(), c.weight.detach(), c.weight_u, c.weight_v, c.weight.grad,
+                                           c.weight_orig.grad) for c in self.convs], sigma=self.sigma)
+            self._bound = bound
+        return self._tab
+
+    @torch.no_grad()
+    def refresh(self, iterate=True):
+        if self.device.type != "cuda":
+            from dsgan_hip import spectral as hsn
+            for i, c in enumerate(self.convs):
+                w, u, v, s = hsn.refresh_torch(c.weight_orig.detach(), c.weight_u, c.weight_v, iterate)
+                c.weight_u.copy_(u)
+                c.weight_v.copy_(v)
+                self.sigma[i] = s
+                if c.weight is None:
+                    c.weight = w.detach().clone()
+                else:
+                    c.weight.copy_(w)
+            return
+        self.table().refresh(iterate)
+        if self.weights is not None:   # the cached tap-major and 16-bit copies of W_sn rebuild in place
+            HF.bump_weight_generation(self.weights)
+
+    @torch.no_grad()
+    def backward(self):
+        if self.device.type != "cuda":
+            raise RuntimeError("SpectralState.backward needs a ROCm GPU (there is no CPU execution path)")
+        self.table().backward()
 
 
 def _fusable(*xs):
@@ -208,6 +353,8 @@ def _patchgan_forward(model, plan, x, pad, sigmoid):
         c = model[idx]
         if use_in is None:      # last conv: raw logits
             h = HF.conv2d(h, c.weight, c.bias, stride=stride, pad=pad)
+        elif use_in and isinstance(model[idx + 1], nn.Identity):   # SN-PatchGAN: no norm layer, LeakyReLU in the epilogue
+            h = HF.conv2d(h, c.weight, c.bias, stride=stride, pad=pad, act="lrelu")
         elif use_in and isinstance(model[idx + 1], nn.BatchNorm2d):
             h = HF.batch_norm(HF.conv2d(h, c.weight, None, stride=stride, pad=pad), model[idx + 1], act="lrelu")
         elif use_in:
@@ -223,34 +370,50 @@ def has_batch_stats(net):
     return any(isinstance(m, nn.modules.batchnorm._BatchNorm) for m in net.modules())
 
 
+def _sn_factories(spectral_norm, norm_layer, first=0):
+    """(conv, norm) constructors of a discriminator: nn.Conv2d and ``norm_layer`` as they are, or, spectrally
+    normalised, SNConv2d holders numbered from ``first`` in construction order (each with a bias,
+    whatever ``bias=`` says) and nn.Identity in the norm layer's place."""
+    if not spectral_norm:
+        return nn.Conv2d, norm_layer
+    count = [int(first)]
+
+    def conv(cin, cout, kernel_size, stride=1, padding=0, bias=True):
+        count[0] += 1
+        return SNConv2d(cin, cout, kernel_size, stride, padding, index=count[0] - 1)
+
+    return conv, (lambda ch: nn.Identity())
+
+
 class NLayerDiscriminator(nn.Module):
     """PatchGAN D, DSGAN/models/networks.py:533-579.  Same ``model.<i>`` Sequential indices as
     the reference (conv holders at 0, 2, 5, 8, 11; ``use_sigmoid`` appends nn.Sigmoid as model.12),
     forward on HIP kernels (_patchgan_forward).  ``norm`` records which normalisation the plan's
     normalised layers use ("instance" or "batch")."""
 
-    def __init__(self, input_nc, ndf=64, n_layers=3, norm_layer=nn.BatchNorm2d, use_sigmoid=False):
+    def __init__(self, input_nc, ndf=64, n_layers=3, norm_layer=nn.BatchNorm2d, use_sigmoid=False, spectral_norm=False):
         super().__init__()
         if type(norm_layer) == functools.partial:
             use_bias = norm_layer.func == nn.InstanceNorm2d
         else:
             use_bias = norm_layer == nn.InstanceNorm2d
-        self.norm = "instance" if use_bias else "batch"
+        self.norm = "spectral" if spectral_norm else "instance" if use_bias else "batch"
+        Conv2d, norm_layer = _sn_factories(spectral_norm, norm_layer)
         kw, padw = 4, 1
-        seq = [nn.Conv2d(input_nc, ndf, kernel_size=kw, stride=2, padding=padw), nn.LeakyReLU(0.2, True)]
+        seq = [Conv2d(input_nc, ndf, kernel_size=kw, stride=2, padding=padw), nn.LeakyReLU(0.2, True)]
         self.plan = [(0, 2, False)]  # (index, stride, normalised)
         nf_mult = 1
         for n in range(1, n_layers):
             nf_prev, nf_mult = nf_mult, min(2 ** n, 8)
             self.plan.append((len(seq), 2, True))
-            seq += [nn.Conv2d(ndf * nf_prev, ndf * nf_mult, kernel_size=kw, stride=2, padding=padw, bias=use_bias),
+            seq += [Conv2d(ndf * nf_prev, ndf * nf_mult, kernel_size=kw, stride=2, padding=padw, bias=use_bias),
                     norm_layer(ndf * nf_mult), nn.LeakyReLU(0.2, True)]
         nf_prev, nf_mult = nf_mult, min(2 ** n_layers, 8)
         self.plan.append((len(seq), 1, True))
-        seq += [nn.Conv2d(ndf * nf_prev, ndf * nf_mult, kernel_size=kw, stride=1, padding=padw, bias=use_bias),
+        seq += [Conv2d(ndf * nf_prev, ndf * nf_mult, kernel_size=kw, stride=1, padding=padw, bias=use_bias),
                 norm_layer(ndf * nf_mult), nn.LeakyReLU(0.2, True)]
         self.plan.append((len(seq), 1, None))
-        seq += [nn.Conv2d(ndf * nf_mult, 1, kernel_size=kw, stride=1, padding=padw)]
+        seq += [Conv2d(ndf * nf_mult, 1, kernel_size=kw, stride=1, padding=padw)]
         self.use_sigmoid = bool(use_sigmoid)
         if use_sigmoid:
             seq += [nn.Sigmoid()]
@@ -264,26 +427,28 @@ class NLayerDiscriminator_multi(nn.Module):
     """One scale of the multi-scale D, DSGAN/models/networks.py:582-631 (getIntermFeat=False): the
     PatchGAN with ``padw = ceil(1.5) = 2``, a bias on every conv and channels doubling up to 512."""
 
-    def __init__(self, input_nc, ndf=64, n_layers=3, norm_layer=nn.BatchNorm2d, use_sigmoid=False, getIntermFeat=False):
+    def __init__(self, input_nc, ndf=64, n_layers=3, norm_layer=nn.BatchNorm2d, use_sigmoid=False, getIntermFeat=False,
+                 spectral_norm=False, sn_first=0):
         super().__init__()
         if getIntermFeat:
             raise NotImplementedError("NLayerDiscriminator_multi: getIntermFeat=True is not on the DS-GAN path")
         self.n_layers = n_layers
+        Conv2d, norm_layer = _sn_factories(spectral_norm, norm_layer, sn_first)
         kw = 4
         self.padw = padw = int(math.ceil((kw - 1.0) / 2))
-        seq = [nn.Conv2d(input_nc, ndf, kernel_size=kw, stride=2, padding=padw), nn.LeakyReLU(0.2, True)]
+        seq = [Conv2d(input_nc, ndf, kernel_size=kw, stride=2, padding=padw), nn.LeakyReLU(0.2, True)]
         self.plan = [(0, 2, False)]
         nf = ndf
         for n in range(1, n_layers):
             nf_prev, nf = nf, min(nf * 2, 512)
             self.plan.append((len(seq), 2, True))
-            seq += [nn.Conv2d(nf_prev, nf, kernel_size=kw, stride=2, padding=padw), norm_layer(nf),
+            seq += [Conv2d(nf_prev, nf, kernel_size=kw, stride=2, padding=padw), norm_layer(nf),
                     nn.LeakyReLU(0.2, True)]
         nf_prev, nf = nf, min(nf * 2, 512)
         self.plan.append((len(seq), 1, True))
-        seq += [nn.Conv2d(nf_prev, nf, kernel_size=kw, stride=1, padding=padw), norm_layer(nf), nn.LeakyReLU(0.2, True)]
+        seq += [Conv2d(nf_prev, nf, kernel_size=kw, stride=1, padding=padw), norm_layer(nf), nn.LeakyReLU(0.2, True)]
         self.plan.append((len(seq), 1, None))
-        seq += [nn.Conv2d(nf, 1, kernel_size=kw, stride=1, padding=padw)]
+        seq += [Conv2d(nf, 1, kernel_size=kw, stride=1, padding=padw)]
         self.use_sigmoid = bool(use_sigmoid)
         if use_sigmoid:
             seq += [nn.Sigmoid()]
@@ -296,16 +461,18 @@ class NLayerDiscriminator_multi(nn.Module):
 class PixelDiscriminator(nn.Module):
     """DSGAN/models/networks.py:634-656: three 1x1 convs (``net.{0,2,5}``) on the pointwise kernels."""
 
-    def __init__(self, input_nc, ndf=64, norm_layer=nn.BatchNorm2d, use_sigmoid=False):
+    def __init__(self, input_nc, ndf=64, norm_layer=nn.BatchNorm2d, use_sigmoid=False, spectral_norm=False):
         super().__init__()
         if type(norm_layer) == functools.partial:
             use_bias = norm_layer.func == nn.InstanceNorm2d
         else:
             use_bias = norm_layer == nn.InstanceNorm2d
-        net = [nn.Conv2d(input_nc, ndf, kernel_size=1, stride=1, padding=0), nn.LeakyReLU(0.2, True),
-               nn.Conv2d(ndf, ndf * 2, kernel_size=1, stride=1, padding=0, bias=use_bias), norm_layer(ndf * 2),
+        self.spectral_norm = bool(spectral_norm)
+        Conv2d, norm_layer = _sn_factories(spectral_norm, norm_layer)
+        net = [Conv2d(input_nc, ndf, kernel_size=1, stride=1, padding=0), nn.LeakyReLU(0.2, True),
+               Conv2d(ndf, ndf * 2, kernel_size=1, stride=1, padding=0, bias=use_bias), norm_layer(ndf * 2),
                nn.LeakyReLU(0.2, True),
-               nn.Conv2d(ndf * 2, 1, kernel_size=1, stride=1, padding=0, bias=use_bias)]
+               Conv2d(ndf * 2, 1, kernel_size=1, stride=1, padding=0, bias=use_bias)]
         self.use_sigmoid = bool(use_sigmoid)
         if use_sigmoid:
             net.append(nn.Sigmoid())
@@ -314,7 +481,10 @@ class PixelDiscriminator(nn.Module):
     def forward(self, x):
         c0, c2, c5 = self.net[0], self.net[2], self.net[5]
         h = HF.conv2d(x, c0.weight, c0.bias, act="lrelu")
-        h = HF.instance_norm(HF.conv2d(h, c2.weight, c2.bias), act="lrelu")
+        if self.spectral_norm:   # no norm layer: LeakyReLU in the conv epilogue
+            h = HF.conv2d(h, c2.weight, c2.bias, act="lrelu")
+        else:
+            h = HF.instance_norm(HF.conv2d(h, c2.weight, c2.bias), act="lrelu")
         h = HF.conv2d(h, c5.weight, c5.bias)
         return HF.sigmoid(h) if self.use_sigmoid else h
 
@@ -327,14 +497,15 @@ class MultiscaleDiscriminator(nn.Module):
     pool: the two data-grads meet in one buffer (HF.share)."""
 
     def __init__(self, input_nc, ndf=64, n_layers=3, norm_layer=nn.BatchNorm2d, use_sigmoid=False, num_D=3,
-                 getIntermFeat=False):
+                 getIntermFeat=False, spectral_norm=False):
         super().__init__()
         if getIntermFeat:
             raise NotImplementedError("MultiscaleDiscriminator: getIntermFeat=True is not on the DS-GAN path")
         self.num_D, self.n_layers, self.getIntermFeat = num_D, n_layers, False
         self.use_sigmoid = bool(use_sigmoid)
         for i in range(num_D):
-            netD = NLayerDiscriminator_multi(input_nc, ndf, n_layers, norm_layer, use_sigmoid, False)
+            netD = NLayerDiscriminator_multi(input_nc, ndf, n_layers, norm_layer, use_sigmoid, False,
+                                             spectral_norm=spectral_norm, sn_first=i * (n_layers + 2))
             setattr(self, "layer" + str(i), netD.model)
             self.plan, self.padw = netD.plan, netD.padw
         self.downsample = nn.AvgPool2d(3, stride=2, padding=[1, 1], count_include_pad=False)

@@ -51,6 +51,12 @@ Deliberate, documented deviations:
     pairs), its real batch, and backward_G's fake batch, in that order: three calls of one counter-based
     stream per optimize_parameters.  The op (HF.diffaug_cat) also forms the D input, so it replaces the
     concatenation's copy; the G step's gradient flows back through it.  The image losses see the plain fake_B.
+  * --spectral_norm (off by default): the SN-PatchGAN (Miyato et al., ICLR 2018): every D conv reads
+    W_sn = weight_orig / sigma, no norm layer, LeakyReLU in the conv epilogue.  W_sn is refreshed once per D
+    weight version (at construction and right after every optimizer_D.step(), applied or skipped: one batched
+    call, csrc/spectral.hip), so the D step's two passes and the next G step's D pass read the same buffers,
+    and the D backward needs one projection of the accumulated weight grads onto weight_orig.grad
+    (networks.SpectralState.backward), before the D all-reduce and the scaler check.
 """
 import contextlib
 import os
@@ -132,8 +138,10 @@ class Pix2PixModel(BaseModel):
         if self.isTrain:
             use_sigmoid = opt.no_lsgan
             d_in = opt.input_nc + opt.output_nc if self.use_condition == 1 else opt.input_nc
+            sn = bool(getattr(opt, "spectral_norm", False))
             self.netD = networks.define_D(d_in, opt.ndf, opt.which_model_netD, opt.n_layers_D,
-                                          opt.norm, use_sigmoid, opt.init_type, self.gpu_ids)
+                                          opt.norm, use_sigmoid, opt.init_type, self.gpu_ids,
+                                          **({"spectral_norm": True} if sn else {}))
         if self.isTrain:
             W, r = hdist.world_size(), hdist.rank()
             # one process: the global python `random`, consumed exactly as the reference does
@@ -154,6 +162,11 @@ class Pix2PixModel(BaseModel):
             self.g_buckets = hdist.GradBuckets(self.flatG.grad, self.flatG.layout) if W > 1 else None
             hdist.broadcast_params(self.flatG)
             hdist.broadcast_params(self.flatD)
+            # --spectral_norm: the D's SpectralState (None with the flag off); weight_orig now lives in the flat
+            # buffer (and may be rank 0's): W_sn and sigma again from it, with the (u, v) construction left
+            self.snD = getattr(self.netD, "spectral", None)
+            if self.snD is not None:
+                self.snD.refresh(iterate=False)
             self.optimizers = []
             fp16 = HF.get_precision() == "fp16"
             guard = int(getattr(opt, "nonfinite_guard", -1))
@@ -517,11 +530,15 @@ class Pix2PixModel(BaseModel):
             self.set_requires_grad(self.netD, True)
             self.optimizer_D.zero_grad()
             self.backward_D(fake_AB)
+            if self.snD is not None:   # the W_sn leaves' accumulated grads, projected onto weight_orig.grad
+                self.snD.backward()
             if self.exchange:
                 hdist.allreduce_mean_(self.flatD.grad, force=True)
             if self.scaler_D is not None:
                 self.scaler_D.check(self.flatD.grad)
             self.optimizer_D.step()
+            if self.snD is not None:   # one power iteration per weight version, applied step or skipped
+                self.snD.refresh()
         else:
             self.loss_D_fake = 0
             self.loss_D_real = 0

@@ -49,6 +49,13 @@ class TrainOptions(BaseOptions):
         parser.add_argument("--diffaug", type=_diffaug_policy, default="",
                             help="augment the discriminator's input: a comma-separated subset of "
                                  "color,translation,cutout (empty: off)")
+        # build extension: the SN-PatchGAN (Miyato et al., ICLR 2018).  Every conv of the discriminator is
+        # spectrally normalised (one power iteration per D weight version, on HIP kernels), the norm layers
+        # leave (they would cancel the rescaling) and LeakyReLU moves into the conv epilogue.  It bounds how
+        # sharp the discriminator can get; --diffaug is the remedy for one that memorises.
+        parser.add_argument("--spectral_norm", action="store_true",
+                            help="spectrally normalised discriminator without norm layers (SN-PatchGAN), any "
+                                 "--which_model_netD; --norm then only steers the generator")
         self.isTrain = True
         return parser
 

@@ -689,6 +689,26 @@ int dsgan_diffaug_bwd(const float* dy, long dy_bs, float* dx, long dx_bs, int N,
                       int policy, long seed, long stream_id, const long* used, int group,
                       float* ws, long ws_elems, hipStream_t stream);
 int dsgan_diffaug_params(float* out, int n, long seed, long stream_id, long call, int H, int W, hipStream_t stream);
+/* ---- spectral normalisation of the discriminator's conv weights (spectral.hip; --spectral_norm) ----
+ * One call covers the n layers of a discriminator.  desc is a DEVICE table of n rows of
+ * dsgan_sn_fields() longs: the addresses of W [R][C] (the conv weight [Cout][Cin kh kw] in the flat
+ * parameter buffer), W_sn [R][C], u [R], v [C], sigma [1], the temporaries t [C], a [R] and
+ * part [dsgan_sn_parts(R, C)], the scratch G [R][C] the weight-grad kernels accumulated into and
+ * dW [R][C] (weight_orig's gradient); then R and C.  max_r / max_c: the largest R and C of the table
+ * (they size the grids; a layer uses its own extent).  fp32 in every precision mode; eps = 1e-12.
+ * _refresh, iterate != 0: one power iteration, torch.nn.utils.spectral_norm's training forward:
+ *     v <- W^T u / max(|W^T u|, eps);  a = W v;  u <- a / max(|a|, eps);  sigma = u . a;  W_sn = W / sigma
+ *   iterate == 0: u and v are kept; a = W v, sigma = u . a and W_sn are recomputed by the same code,
+ *   so that it reproduces the sigma and W_sn bits of the iterating call that left (u, v).
+ * _backward: dW += (G - <G, W_sn> u v^T) / sigma (u, v constants, as in torch), then G <- 0.  G and
+ *   dW are not read by _refresh and may be NULL in a table only it uses.
+ * Every sum has one fixed order that depends on R and C alone: no atomics, the same bits from two
+ * runs and from a batched call and the same layers called one at a time.  Dependent phases are
+ * separate launches (3 for an iterating refresh, 2 otherwise, 2 for the backward). */
+int dsgan_sn_fields(void);
+long dsgan_sn_parts(int R, int C);
+int dsgan_sn_refresh(const long* desc, int n, int max_r, int max_c, int iterate, hipStream_t stream);
+int dsgan_sn_backward(const long* desc, int n, int max_r, int max_c, hipStream_t stream);
 /* input pipeline, DSGAN/data/aligned_dataset.py:38-86 (ToTensor, crop, Normalize(0.5,0.5), flip,
  * optional gray): src uint8 [N][H][W][3] (already cropped), flip int [N] (device), dst fp32
  * [N][3 or 1][H][W]; bit-exact with the reference's torch CPU transforms. */
